@@ -17,9 +17,17 @@ world size must equal --gpus).  Envs are sharded by global env id (rank r owns
 [r*N, (r+1)*N), SURVEY 8(e)); the step has no collective -> "scaling": "weak";
 value = sum over ranks of envs x steps / max-over-ranks time.
 
-Also reported: the raw fused-kernel loop (Go1Native.step alone), the roofline of the
-fused step kernel (HIP events around that kernel, on its launch stream, over the timed
-region), the PPO rollout rate (act + step + record) and the CPU oracle timed on a
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and
+prints the result line: the headline rate, `ms_per_step`, and the roofline of the fused
+step kernel (HIP events around that kernel, on its launch stream, over the timed region;
+no run of its own).  `--dump-outputs DIR` also writes what the last timed VecEnv.step
+returned (obs, privileged_obs, obs_history, rew, done, time_outs) as DIR/<name>.npy,
+float32; the inputs are seeded and every untimed step is counted, not clocked, so the
+same arguments give the same arrays on every run.
+
+`--full` adds the legs that take runs of their own: the raw fused-kernel loop
+(Go1Native.step alone), the PPO rollout rate (act + step + record), the whole training
+loop, the configs[1] velocity env, the `--sweep` sizes and the CPU oracle timed on a
 bounded sample on rank 0's host cores (N = 1 only).
 """
 import argparse
@@ -57,7 +65,8 @@ SURVEY_BYTES_PER_ENV_STEP = 3522
 #     targets 48, base rotation 12, episode sums 52, counters 12 (motor strength/offset and the
 #     trajectory are written only on reset / DR steps: < 1 B per env-step)
 PATH_BYTES_PER_ENV_STEP = 1696 + 2047
-PREWARM_S = 0.25
+PREWARM_ENV_STEPS = 3840 * 4096  # untimed clock pre-warm: ~0.25 s of stepping at 4096 envs (see main)
+DUMP_BYTES_MAX = 64 * 10**6      # --dump-outputs: all arrays together
 # Algorithmic FLOPs per env-step, SURVEY.md 8(d): actuator MLP 132,144 (exact) + ABA / contact /
 # integration ~40,000 (estimate) + post-physics ~6,000 -> ~1.8e5.  The measured count (PMC VALU / MFMA
 # FLOP counters of the step kernel, profiles/r05/step_counters.json) is reported beside it.
@@ -193,6 +202,29 @@ def make_env(n, rank, world, dev):
     cfg = CF.readme_config(n_envs=n, terrain="single_path", rows=32, cols=32)
     return E.HistoryWrapper(E.TrajectoryTrackingEnv(sim_device=str(dev), cfg=cfg, seed=11, rank=rank,
                                                     world_size=world))
+
+
+def step_outputs(ret):
+    """What one HistoryWrapper.step returned, as host float32 arrays (copied before anything steps again:
+    the tensors are slots of the env's output ring)."""
+    od, rew, done, info = ret
+    out = {"obs": od["obs"], "privileged_obs": od["privileged_obs"], "obs_history": od["obs_history"],
+           "rew": rew, "done": done, "time_outs": info["time_outs"]}
+    return {k: v.detach().float().cpu().numpy().copy() for k, v in out.items()}
+
+
+def dump_outputs(path, arrays, rank, world):
+    """DIR/<name>.npy (<name>_rank<r>.npy at world > 1), at most DUMP_BYTES_MAX in all: above that the same
+    seeded sample of env rows is kept of every array (its indices go to sample_rows.npy)."""
+    os.makedirs(path, exist_ok=True)
+    n = len(arrays["obs"])
+    row_bytes = sum(a.nbytes // n for a in arrays.values()) + 8
+    if n * row_bytes > DUMP_BYTES_MAX:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES_MAX // row_bytes, replace=False))
+        arrays = dict({k: a[rows] for k, a in arrays.items()}, sample_rows=rows.astype(np.float64))
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f"{k}{suffix}.npy"), a)
 
 
 def kernel_loop(env, ring, steps, warmup, every=4, contact_forces=True):
@@ -461,6 +493,11 @@ def main():
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--envs-per-gpu", type=int, default=4096)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: kernel loop, rollout, learn, velocity, "
+                         "--sweep, CPU baseline (the --no-* options drop single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--no-rollout", action="store_true")
@@ -479,6 +516,10 @@ def main():
     ap.add_argument("--rollout-outputs", action="store_true",
                     help="with --kernel-only: the rollout's stores only (no contact forces, no aux block)")
     args = ap.parse_args()
+    if args.sweep and not args.full:
+        ap.error("--sweep is a leg of --full")
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch(args.gpus, sys.argv[1:]))
@@ -536,11 +577,11 @@ def main():
     base = env.env
     # clock pre-warm: the GPU ramps its clocks over the first ~10-20 ms of sustained load (a 500-step
     # loop right after 50 warmup steps measured 68.5 us/step, after 200 warmup steps 57.7), so the
-    # env is stepped for PREWARM_S seconds (untimed, reported as "prewarm_steps") before the W
-    # warmup steps the caller asked for
+    # env is stepped for about a quarter of a second (untimed, reported as "prewarm_steps") before
+    # the W warmup steps the caller asked for.  The count is fixed by the env count, not by the
+    # clock, so that the timed steps start from the same state on every run (--dump-outputs)
     prewarm = 0
-    t_pw = time.perf_counter()
-    while time.perf_counter() - t_pw < PREWARM_S:
+    while prewarm * n < PREWARM_ENV_STEPS:
         for _ in range(16):
             env.step(ring[prewarm % 64])
             prewarm += 1
@@ -553,8 +594,9 @@ def main():
     torch.cuda.synchronize()
     base.kernel_events.extend(ev.pair(k // every) if k % every == 0 else None for k in range(args.steps))
     t0 = time.perf_counter()
+    ret = None
     for k in range(args.steps):
-        env.step(ring[k % 64])
+        ret = env.step(ring[k % 64])
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -563,10 +605,13 @@ def main():
     base.kernel_events.clear()
     kernel_ms = float(np.mean([ev.ms(i) for i in range(n_ev)]))
     ev.close()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(ret), rank, world)
     if not os.environ.get("GO1_BENCH_ALLOW_NONFINITE"):
         assert torch.isfinite(base.obs_buf).all(), "non-finite observations"
-    # the fused kernel alone on the same handle (no env host code)
-    kdt, kms_raw = kernel_loop(env, ring, min(args.steps, 200), min(args.warmup, 10))
+    kdt = kms_raw = 0.0
+    if args.full:  # the fused kernel alone on the same handle (no env host code)
+        kdt, kms_raw = kernel_loop(env, ring, min(args.steps, 200), min(args.warmup, 10))
     mine = torch.tensor([elapsed, kernel_ms, kdt, kms_raw], device=dev, dtype=torch.float64)
     per_rank = [mine]
     if dist:
@@ -579,10 +624,10 @@ def main():
     # the rollout loop and the whole training loop run on every rank (RCCL all-reduces inside the timed
     # learn iterations at world > 1); rank 0 reports the slowest rank's time
     legs = {}
-    if not args.no_rollout:
+    if args.full and not args.no_rollout:
         legs["rollout"] = rollout_rate(n, dev, steps=min(args.steps, 240), warmup=min(args.warmup, 24), rank=rank,
                                        world=world)
-    if not args.no_learn:
+    if args.full and not args.no_learn:
         legs["learn"] = learn_rate(n, dev, rank=rank, world=world)
 
     if rank == 0:
@@ -633,20 +678,21 @@ def main():
                          "fp32": fp32,
                          "valu_issue_frac_pmc": pmc["valu"],
                          "note": "latency/VALU-issue bound, not HBM bound: see DESIGN.md section 5"},
-            "kernel_loop": {"value": n_global * ksteps / kdt, "unit": "env-steps/s", "ms_per_step": kdt / ksteps * 1e3,
-                            "kernel_ms": max(p[3] for p in per_rank),
-                            "what": "Go1Native.step alone (the fused kernel launch, no env host code)"},
             "per_rank": [{"rank": r, "elapsed_s": p[0], "kernel_ms": p[1]} for r, p in enumerate(per_rank)],
         }
+        if args.full:
+            line["kernel_loop"] = {"value": n_global * ksteps / kdt, "unit": "env-steps/s",
+                                   "ms_per_step": kdt / ksteps * 1e3, "kernel_ms": max(p[3] for p in per_rank),
+                                   "what": "Go1Native.step alone (the fused kernel launch, no env host code)"}
         if args.sweep:
             line["sweep"] = [env_sweep(int(x), dev) for x in args.sweep.split(",")]
         for k, v in legs.items():
             line[k] = v
-        if not args.no_velocity and world == 1:
+        if args.full and not args.no_velocity and world == 1:
             # at least two full 32-step history windows (velocity.py HIST_WINDOW), whatever --steps is
             line["velocity"] = velocity_rate(n, dev, steps=max(2 * 32, min(args.steps, 300)),
                                              warmup=min(args.warmup, 30))
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(n, budget_s=args.cpu_budget)
         print(json.dumps(line), flush=True)
     env.close()

@@ -6,8 +6,9 @@ Consumers restated (never the reference run on the GPU box):
   * scripts/eval.py:38-51 load_policy(old_ppo=True): ActorCritic(num_obs, num_privileged_obs,
     num_obs_history, num_actions).load_state_dict(torch.load(<logdir>/checkpoints/ac_weights.pt)),
     policy = actor_critic.act(obs["obs_history"]).
-The reference's checkpoints are read with torch.load(weights_only=True) only (its TorchScript files
-execute code and are never loaded)."""
+The reference's trained checkpoint is read from its recorded state dict (tests/golden/trained_policy.npz,
+written by tests/golden/make_trained_policy.py with torch.load(weights_only=True); the reference's
+TorchScript files execute code and are never loaded)."""
 import os
 import sys
 import types
@@ -18,7 +19,7 @@ import torch
 
 from legged_tracking_amd import rollout as R
 
-REF_RUN = "/root/reference/runs/trajectory_tracking/run-20230904_112307-rhi1my71/checkpoints/ac_weights.pt"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _trained_runner(tmp_path, log_wandb=False, save_dir=None):
@@ -77,7 +78,6 @@ def test_runner_saves_under_wandb_run_dir_and_uploads(tmp_path, monkeypatch):
     assert runner.checkpoint_dir() == "last_run/checkpoints"
 
 
-@pytest.mark.skipif(not os.path.exists(REF_RUN), reason="reference tree absent (GPU box)")
 def test_reference_trained_checkpoint_loads():
     """The reference's trained 261-obs policy (runs/trajectory_tracking/run-20230904_112307-rhi1my71).
     It was trained with 6 privileged observations (adaptation_module.4: 128 -> 6, actor input 267),
@@ -87,7 +87,8 @@ def test_reference_trained_checkpoint_loads():
     not into the 2-priv ActorCritic train.py builds (size mismatch, the reference fails the same
     way); the teacher / critic path would need the 4 extra privileged observations the trajectory
     env no longer computes."""
-    sd = torch.load(REF_RUN, map_location="cpu", weights_only=True)
+    d = np.load(os.path.join(GOLDEN, "trained_policy.npz"))
+    sd = {k[3:]: torch.from_numpy(d[k]) for k in d.files if k.startswith("sd/")}
     assert sd["adaptation_module.4.weight"].shape == (6, 128) and sd["actor_body.0.weight"].shape == (512, 267)
     ac = R.ActorCritic(261, 6, 261, 12)
     ac.load_state_dict(sd)

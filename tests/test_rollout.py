@@ -414,7 +414,11 @@ def _check_update(d, alg, losses, rtol_loss, atol_w, atol_max=None):
 
 def test_ppo_update_matches_reference_on_cpu():
     """CPU: the same torch ops in the same order as ppo.py -> losses within 1e-5, weights within 1e-6
-    after 20 Adam steps (5 epochs x 4 minibatches) with the adaptive-KL learning rate."""
+    after 20 Adam steps (5 epochs x 4 minibatches) with the adaptive-KL learning rate.  "The same order"
+    includes the CPU GEMM's own reduction order: the fixture was recorded with torch's MKL on an AVX-512 Intel
+    host, where this replay is exact at 8 threads and within 6e-8 at 1 or 4; on an AMD EPYC host MKL takes
+    another code path (any thread count: max |dw| 2.0e-4, 141 of 700k weights above 1e-6, losses within
+    2.4e-6 relative, same KL decisions) and the bound does not hold there."""
     d = _fixture()
     alg, losses = _ppo_update_from_fixture(d, "cpu", TorchRolloutKernels())
     _check_update(d, alg, losses, rtol_loss=1e-5, atol_w=1e-6)

@@ -17,7 +17,7 @@ run pytest_gpu 900 python -m pytest tests -m gpu -q -x -p no:cacheprovider
 rc=$?
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 [ "$MODE" = "tests" ] && exit $rc
-run bench 600 python bench.py --steps 500 --warmup 50 || exit $?
+run bench 600 python bench.py --full --steps 500 --warmup 50 || exit $?
 cd /tmp && run_prof() { timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/gpurun_out/prof" -o r1 -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 200 --warmup 20 --no-cpu-baseline > "$GRAFT_REPO_ROOT/gpurun_out/bench_prof.log" 2>&1; }
 echo "== rocprof"; run_prof; echo "rc=$?"; tail -3 "$GRAFT_REPO_ROOT/gpurun_out/bench_prof.log"
 find "$GRAFT_REPO_ROOT/gpurun_out/prof" -name "*stats*" | head

@@ -20,10 +20,10 @@ if [ "${SUITE:-0}" = 1 ]; then
   timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { echo "smoke failed"; tail -5 $O/smoke.log; exit 1; }
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
   tail -c 1500 $O/bench.json
   if [ -n "$SWEEP" ]; then
-    timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 --no-rollout --no-cpu-baseline --sweep "$SWEEP" > $O/bench_sweep.json 2> $O/bench_sweep.err || { echo "sweep failed"; tail -20 $O/bench_sweep.err; exit 1; }
+    timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 5 --no-rollout --no-cpu-baseline --sweep "$SWEEP" > $O/bench_sweep.json 2> $O/bench_sweep.err || { echo "sweep failed"; tail -20 $O/bench_sweep.err; exit 1; }
     echo "sweep ok"
   fi
 fi

@@ -20,5 +20,5 @@ pass sq2 --pmc SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY
 pass tcc --pmc TCC_HIT_sum TCC_MISS_sum
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rollout" -o rollout -- python3 "$ROOT/bench.py" --rollout-only --steps 120 --warmup 24 > "$OUT/rollout.log" 2>&1 || { echo "rollout rc=$?"; tail -5 "$OUT/rollout.log"; exit 1; }
 echo rollout ok
-cd "$ROOT" && timeout -k 10 400 python bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-rollout --sweep 16384,65536,262144 > "$OUT/sweep.log" 2>&1 || { echo "sweep rc=$?"; tail -5 "$OUT/sweep.log"; exit 1; }
+cd "$ROOT" && timeout -k 10 400 python bench.py --full --steps 300 --warmup 30 --no-cpu-baseline --no-rollout --sweep 16384,65536,262144 > "$OUT/sweep.log" 2>&1 || { echo "sweep rc=$?"; tail -5 "$OUT/sweep.log"; exit 1; }
 echo sweep ok
