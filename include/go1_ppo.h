@@ -60,7 +60,8 @@ typedef struct go1_ppo_hyper {
   float desired_kl;              /* <= 0: no adaptive schedule (desired_kl None or schedule != "adaptive") */
   float use_clipped_value_loss;  /* 0 / 1 */
   float selective;               /* selective_adaptation_module_loss: 0 / 1 (column 0 only) */
-  float beta1, beta2, eps;       /* Adam (both optimizers) */
+  float beta1, beta2, eps;       /* Adam (both optimizers); the betas are read as their 7-significant-digit decimal
+                                    (0.999f -> 0.999 in double), so that 1 - beta is torch's, not 1 - the f32 rounding */
   float world;                   /* ranks the gradients are summed over (1 without a process group) */
   float adaptation_lr;           /* adaptation_module_learning_rate */
 } go1_ppo_hyper;
@@ -93,7 +94,9 @@ int go1_ppo_workspace_bytes(const go1_ppo_dims* d, int64_t* bytes);
 int go1_ppo_pack(const go1_ppo_dims* d, const go1_ppo_bufs* b, void* stream);
 /* phase 0: main loss gradient into grads (+ aux sums); phase 1: adaptation-loss gradient into the adaptation
    slice of grads (+ aux).  At world > 1 the caller all-reduces grads[0 : GO1_PPO_AUX + count] (phase 0) or
-   grads[0 : GO1_PPO_AUX + adaptation count] (phase 1) between go1_ppo_grad and go1_ppo_step. */
+   grads[0 : GO1_PPO_AUX + adaptation count] (phase 1) between go1_ppo_grad and go1_ppo_step.
+   mb < 5 is refused with GO1_PPO_E_ARG: the adaptation loss trains on num_train = mb / 5 * 4 rows (ppo.py:165),
+   none below 5 (the reference's loss is NaN there).  The layout queries above accept any mb >= 1. */
 int go1_ppo_grad(const go1_ppo_dims* d, const go1_ppo_bufs* b, int32_t phase, void* stream);
 /* phase 0: KL -> learning rate, gradient clip, Adam (all parameters), re-pack;
    phase 1: Adam of the adaptation module, re-pack of its weights */

@@ -1237,14 +1237,18 @@ __global__ __launch_bounds__(256) void finalize_kernel(Finalize F) {
   // denom = sqrt(exp_avg_sq) / sqrt(bc2) + eps
   const float step = F.steps[F.phase] + 1.0f;
   F.steps[F.phase] = step;
-  const double b1 = (double)hp.beta1, b2 = (double)hp.beta2;
+  // The betas arrive as f32, and 1 - (double)0.999f is 1.3e-5 (relative) off torch's 1 - 0.999, 1 - (double)0.9f
+  // 2.4e-7 off 1 - 0.9: the moments would drift from torch.optim.Adam's by that much.  Betas are decimal literals:
+  // the double nearest to the f32's 7-significant-digit decimal is the Python float torch computes with (the
+  // f32 spacing below 1 is finer than 1e-7, so the decimal is unambiguous; any other beta moves by < 5e-8).
+  const double b1 = rint((double)hp.beta1 * 1.0e7) / 1.0e7, b2 = rint((double)hp.beta2 * 1.0e7) / 1.0e7;
   const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
   F.scal[0] = gscale;
   F.scal[1] = (float)(-(lr / bc1));
   F.scal[2] = (float)sqrt(bc2);
   F.scal[3] = hp.eps;
   F.scal[4] = (float)(1.0 - b1);
-  F.scal[5] = hp.beta2;
+  F.scal[5] = (float)b2;
   F.scal[6] = (float)(1.0 - b2);
 }
 
@@ -1974,6 +1978,10 @@ int go1_ppo_pack(const go1_ppo_dims* d, const go1_ppo_bufs* b, void* stream) {
 }
 
 int go1_ppo_grad(const go1_ppo_dims* d, const go1_ppo_bufs* b, int32_t phase, void* stream) {
+  // num_train = mb / 5 * 4 (ppo.py:165) is 0 below 5 rows: the adaptation loss would divide by zero (the layout
+  // itself accepts mb >= 1: go1_ppo_param_count is asked with mb = 1)
+  if (d && d->mb < 5)
+    return fail(GO1_PPO_E_ARG, "go1_ppo_grad: mb >= 5 required (num_train = mb / 5 * 4 training rows, ppo.py:165)");
   Ctx C;
   int rc = check_ctx(d, b, C, stream);
   if (rc) return rc;

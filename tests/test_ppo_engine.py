@@ -44,6 +44,13 @@ def test_library_exports_every_go1_ppo_symbol_and_layout_matches_module():
     bad = PE._Dims(hist=261, priv=9, actions=12, mb=384, rows=1536)
     assert lib.go1_ppo_param_count(C.byref(bad), None, None) == -1
     assert b"priv 1..8" in lib.go1_ppo_last_error()
+    # mb < 5 leaves the adaptation loss no training row (num_train = mb // 5 * 4): go1_ppo_grad refuses it before
+    # it touches a buffer; the layout queries (PPOEngine.__init__ asks with mb = 1) accept it
+    few = PE._Dims(hist=261, priv=2, actions=12, mb=4, rows=1536)
+    assert lib.go1_ppo_param_count(C.byref(few), None, None) == 0
+    for phase in (0, 1):
+        assert lib.go1_ppo_grad(C.byref(few), C.byref(PE._Bufs()), phase, None) == -1
+        assert b"mb >= 5" in lib.go1_ppo_last_error()
     # a module the engine does not implement (another activation) falls back to the torch update
     R.AC_Args.activation = "tanh"
     try:
