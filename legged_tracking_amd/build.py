@@ -18,14 +18,15 @@ STEP_FLAGS = ["-fno-slp-vectorize"]
 # name -> (sources, extra dependencies, extra flags)
 LIBS = {
     "libgo1_mi355x.so": (["go1_step.hip", "go1_terrain.hip"],
-                         ["pmath.h", "go1_device.h", "go1_model_consts.h", "go1_spec.h", os.path.join(INC, "go1_mi355x.h")], STEP_FLAGS),
+                         ["pmath.h", "go1_device.h", "go1_step_shared.h", "go1_model_consts.h", "go1_spec.h",
+                          os.path.join(INC, "go1_mi355x.h")], STEP_FLAGS),
     "libgo1_rollout.so": (["rollout.hip"], [os.path.join(INC, "go1_rollout.h")], []),
     "libgo1_ppo.so": (["ppo_update.hip"], [os.path.join(INC, "go1_ppo.h")], []),
     # kernel-argument preloading: the curriculum launch's leading scalar arguments arrive in SGPRs with the wave
     # (11.75-11.78 against 12.02-12.10 us average per launch, alternating runs of one session)
     "libgo1_velocity.so": (["go1_velocity.hip"],
-                           ["pmath.h", "go1_device.h", "go1_model_consts.h", os.path.join(INC, "go1_mi355x.h"),
-                            os.path.join(INC, "go1_velocity.h")],
+                           ["pmath.h", "go1_device.h", "go1_step_shared.h", "go1_model_consts.h",
+                            os.path.join(INC, "go1_mi355x.h"), os.path.join(INC, "go1_velocity.h")],
                            STEP_FLAGS + ["-mllvm", "-amdgpu-kernarg-preload-count=16"]),
 }
 OUT = os.path.join(BUILD, "libgo1_mi355x.so")  # the step library (kept for callers of build())

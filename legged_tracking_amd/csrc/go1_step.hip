@@ -24,6 +24,7 @@
 // integrator uses FMA contraction and native sin/cos (f32, compared with the
 // oracle's f64 integrator within a tolerance).
 #include "go1_device.h"
+#include "go1_step_shared.h"
 
 // =====================================================================
 //                          the fused step kernel
@@ -188,13 +189,14 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const size_t d0 = (size_t)e * NDOF + leg * 3;
   // stored lag (go1_state.lag): the scaled actions of the last K = GO1_LAG_STEPS(decimation) steps,
   // oldest first; the README configuration (decimation 4) keeps K = 2 in the specialised kernel
-  const int dec = c->decimation;
   constexpr int KMAX = SPEC ? 2 : GO1_LAG_SLOTS;
-  const int KL = SPEC ? 2 : GO1_LAG_STEPS(dec);
+  const int KL = SPEC ? 2 : GO1_LAG_STEPS(c->decimation);
   const float* lag_in = st.lag + (size_t)e * 12 * KL + leg * 3;
 
-  // ---------------- load
-  float act[3], q[3], qd[3], eh[2][3], vh[2][3], strength[3], offset[3];
+  // ---------------- load (the per-joint registers; J: their view for the shared sub-step loop)
+  float act[3], q[3], qd[3], eh[2][3], vh[2][3], strength[3], offset[3], dflt[3], tlim[3], lag_pre[KMAX][3];
+  float scaled[3], torque[3], tgt[3];
+  const Joints<KMAX> J = {act, q, qd, eh, vh, strength, offset, dflt, tlim, lag_pre, scaled, torque, tgt};
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     act[j] = clampf(A.actions[d0 + j], -CI(clip_actions), CI(clip_actions));
@@ -209,7 +211,6 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
   // per-joint constants and the stored lag entries the sub-steps read: loaded here so that no
   // sub-step waits on a memory round trip
-  float dflt[3], tlim[3], lag_pre[KMAX][3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     dflt[j] = c->default_dof_pos[leg * 3 + j];
@@ -250,15 +251,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   float my_sum = sub16 < NT ? st.episode_sums[(size_t)e * NS + sub16] : 0.0f;
   float my_tot = sub16 < 3 ? st.episode_sums[(size_t)e * NS + NT + sub16] : 0.0f;
   Phys P;
-  if (!INJ) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      P.pos[i] = st.root[(size_t)e * 13 + i];
-      P.wv[i] = f2{st.root[(size_t)e * 13 + 10 + i], st.root[(size_t)e * 13 + 7 + i]};
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) P.quat[i] = st.root[(size_t)e * 13 + 3 + i];
-  }
+  if (!INJ) phys_load_root(P, st.root + (size_t)e * 13);
   Terr T = {nullptr, CI(hf_nx), CI(hf_ny), CI(horizontal_scale), nullptr, 0, 0};
   // +8 float2 per env: the four envs' patches start 16 banks apart (unpadded they start on the same bank, and
   // the legs sit at similar cells of their env-centred patches: the corner reads of different envs collided)
@@ -357,132 +350,21 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   hold(true);
   asm volatile("" : "+v"(rebind_flag));  // kept in a VGPR: a scalar branch on it would wait early
   if (rebind && sub16 == 0 && rebind_flag) K.prev_extras[e] = rebind_val;
-  float scaled[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    scaled[j] = act[j] * CI(action_scale);
-    if (j == 0) scaled[j] = scaled[j] * CI(hip_scale_reduction);
-  }
 
   // ---------------- decimation loop (:82-88)
-  // The lag ring is pushed once per sim sub-step with the same scaled action
-  // (:973), so sub-step s reads the slot s+1 of the incoming ring and the ring
-  // leaves the step as [old4, old5, old6, scaled x 4].
-  float torque[3], tgt[3];
   float cf_raw[CF_RAW] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, cf_leg[9], cf_base[3], cf_hip[3];
-  for (int sub = 0; sub < dec; ++sub) {
-    MARK(sub_begin);
-    // _compute_torques (:957-996)
-    {
-      // inputs of this lane's three joints ...
-      // the ring's oldest slot after this sub-step's push (:973-974) is old slot sub + 1, i.e. the
-      // scaled action of `back` steps ago (stored entry KL - back), or this step's for back = 0
-      const int m = 6 - sub;
-      const int back = m <= 0 ? 0 : (m + dec - 1) / dec;  // wave-uniform: scalar selects below
-      float xin[3][6];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        float lg = scaled[j];
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) lg = back == KL - k ? lag_pre[k][j] : lg;
-        tgt[j] = lg + dflt[j];
-        const float err = q[j] - tgt[j] + offset[j];
-        xin[j][0] = err; xin[j][1] = eh[0][j]; xin[j][2] = eh[1][j];
-        xin[j][3] = qd[j]; xin[j][4] = vh[0][j]; xin[j][5] = vh[1][j];
-      }
-      // ... -> 3 MFMA groups per wave: group j holds joint j of the 16 (env, leg) items
-      // of the wave in column 4 env + leg; row (= role) q supplies inputs q and 4 + q of
-      // its own leg and receives the item's torque in place.
-      MARK(mlp_begin);
-      float tq[3] = {0.0f, 0.0f, 0.0f};
-      float b0[3], b1v[3];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const float* y = xin[j];
-        b0[j] = sel4(lq, y[0], y[1], y[2], y[3]);
-        b1v[j] = sel4(lq, y[4], y[5], 0.0f, 0.0f);
-      }
-#ifdef GO1_ABL_NO_MLP
-#pragma unroll
-      for (int j = 0; j < 3; ++j) tq[j] = 0.0f * (b0[j] + b1v[j]);  // ablation build only: no actuator net
-#else
-      {
-        MlpFrag Fs;
-        mlp_unpark(Fs, s_mlp, lane);
-        mlp_group3(Fs, b0, b1v, tq);
-      }
-#endif
-#ifdef GO1_ABL_NO_MLP
-#pragma unroll
-      for (int j = 0; j < 3; ++j) tq[j] += -20.0f * xin[j][0] - 0.5f * xin[j][3];  // PD stand-in
-#endif
-      MARK(mlp_done);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        eh[1][j] = eh[0][j];
-        eh[0][j] = xin[j][0];
-        vh[1][j] = vh[0][j];
-        vh[0][j] = qd[j];
-        const float t = tq[j] * strength[j];
-        const float lim = tlim[j];
-        torque[j] = clampf(t, -lim, lim);
-      }
-    }
-    if (INJ) {
-      const float* id = A.inj_dof + ((size_t)sub * n + e) * NDOF * 2;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        q[j] = id[(leg * 3 + j) * 2];
-        qd[j] = id[(leg * 3 + j) * 2 + 1];
-      }
-    } else {
-      const float h = c->sim_dt / (float)c->n_internal;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) { P.q[j] = q[j]; P.qd[j] = qd[j]; }
-      MARK(phys_call);
-#ifndef GO1_ABL_NO_PHYS
-      for (int k = 0; k < c->n_internal; ++k) {
-        const bool last = (sub == dec - 1) && (k == c->n_internal - 1);
-        phys_substep(c, s_phys, P, torque, h, A.sim_gravity, friction, restitution, payload, T, leg, role, last,
-                     cf_raw, s_self[el], sub == 0 && k == 0);
-      }
-#else
-      P.qd[0] += 1e-4f * torque[0]; P.qd[1] += 1e-4f * torque[1]; P.qd[2] += 1e-4f * torque[2];
-#endif
-#pragma unroll
-      for (int j = 0; j < 3; ++j) { q[j] = P.q[j]; qd[j] = P.qd[j]; }
-      MARK(phys_returned);
-    }
-    if (A.dbg_torques && owner) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) A.dbg_torques[((size_t)sub * n + e) * NDOF + leg * 3 + j] = torque[j];
-    }
-  }
-  cf_sum(cf_raw, role, cf_leg, cf_base, cf_hip);
+  step_substeps<INJ>(c, A, J, P, s_mlp, s_phys, T, s_self[el], cf_raw, KL, friction, restitution, payload, e, lane,
+                     CI(action_scale), CI(hip_scale_reduction), leg, role);
+  contact_totals<INJ>(cf_raw, A.inj_contact, e, leg, role, cf_leg, cf_base, cf_hip);
   hold(false);
   float root[13];
   if (INJ) {
 #pragma unroll
     for (int i = 0; i < 13; ++i) root[i] = A.inj_root[(size_t)e * 13 + i];
-    const float* ic = A.inj_contact + (size_t)e * NB * 3;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      cf_base[i] = ic[i];
-      cf_hip[i] = ic[(1 + leg * 4) * 3 + i];
-    }
-#pragma unroll
-    for (int b = 0; b < 3; ++b)
-#pragma unroll
-      for (int i = 0; i < 3; ++i) cf_leg[b * 3 + i] = ic[(2 + leg * 4 + b) * 3 + i];
   } else {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      root[i] = P.pos[i]; root[7 + i] = P.wv[i].y; root[10 + i] = P.wv[i].x;
-    }
-    root[0] = P.pos[0] + org_x;
+    phys_store_root(P, root);
+    root[0] = P.pos[0] + org_x;  // back to the world frame (the integrator ran relative to the terrain origin)
     root[1] = P.pos[1] + org_y;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) root[3 + i] = P.quat[i];
   }
   // height scan (:1918-1965) samples at the post-physics, pre-reset pose: the gathers are
   // issued here and consumed by the height observations at the end
@@ -529,14 +411,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     if (scan) sample(x_start + p / GO1_GRID_Y, p % GO1_GRID_Y, hv[k][0], hv[k][1]);
   }
 
-  if (A.contact_forces && owner) {
-    float* o = A.contact_forces + (size_t)e * NB * 3;
-    if (leg == 0) { o[0] = cf_base[0]; o[1] = cf_base[1]; o[2] = cf_base[2]; }
-    float* ol = o + (1 + leg * 4) * 3;
-    ol[0] = cf_hip[0]; ol[1] = cf_hip[1]; ol[2] = cf_hip[2];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) ol[3 + i] = cf_leg[i];
-  }
+  if (A.contact_forces && owner) contact_store(A.contact_forces, e, leg, cf_leg, cf_base, cf_hip);
 
   MARK(post_begin);
   // ================= post_physics_step (:114-169), contraction off =================
@@ -559,18 +434,11 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
   MARK(post_kin_done);
   // DR every rand_interval (:822-824)
-  // slots 34 .. 46 = Philox blocks 8 .. 11: lane sub16 < 4 of the env draws block 8 + sub16 and the
-  // env's lanes read their slots back from LDS (one evaluation per lane instead of four in a row; one
-  // wave per block: its LDS operations complete in order)
+  // slots 34 .. 46 = Philox blocks 8 .. 11, staged through LDS (rng_stage)
   __shared__ float s_u[SEPB][32];
   const bool dr_step = ep % CI(rand_interval) == 0;
   if (dr_step) {
-    if (sub16 < 4) {
-      float uq[4];
-      rng.quad(8 + sub16, uq);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s_u[el][4 * sub16 + k] = uq[k];
-    }
+    rng_stage(rng, 8, 4, sub16, s_u[el]);
     const float sv = s_u[el][34 - 32] * CI(strength_range) + CI(strength_lo);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
@@ -597,16 +465,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   if (CI(terminate_end_of_trajectory) && reached && (float)ep > CI(t_reach)) reset = true;  // (:211-213)
   if (CI(use_terminal_body_rotation) && pg[2] > 0.0f) reset = true;                        // (:215-216)
   if (!INJ) {
-    // native-integrator divergence guard (no reference counterpart: PhysX does not
-    // return non-finite states): an env whose state is not finite, or beyond
-    // GO1_DIVERGED in any component, is reset, and nothing of its diverged state reaches
-    // an output (zero reward, post-reset observations, see below)
-    bool finite = true;
-#pragma unroll
-    for (int i = 0; i < 13; ++i) finite = finite & (fabsf(root[i]) < GO1_DIVERGED);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) finite = finite & (fabsf(q[j]) < GO1_DIVERGED) & (fabsf(qd[j]) < GO1_DIVERGED);
-    diverged = qsum(finite ? 0.0f : 1.0f) != 0.0f;
+    diverged = state_diverged(root, q, qd);
     if (diverged) reset = true;
     if (diverged && sub16 == 0 && A.diverged_count) atomicAdd((unsigned long long*)A.diverged_count, 1ull);
   }
@@ -799,14 +658,8 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // at one atomic per wave; the host orders the rows by (tag, env) as the reference logs them
   int log_row = -1;
   if (compact) {
-    const uint64_t rmask = __ballot(reset && owner && leg == 0);  // lane 4 el: env el's role 0, leg 0
-    if (rmask != 0ull) {
-      int base = 0;
-      if (lane == 0) base = atomicAdd(A.episode_log_count, __popcll(rmask));
-      base = __shfl(base, 0);
-      log_row = base + __popcll(rmask & ((1ull << (4 * el)) - 1ull));
-      if (log_row >= A.episode_log_cap) log_row = -1;  // dropped; the count keeps it (the host reports overflow)
-    }
+    log_row = wave_alloc_row(reset && owner && leg == 0, A.episode_log_count, lane, 4 * el);  // lane 4 el: env el's role 0, leg 0
+    if (log_row >= A.episode_log_cap) log_row = -1;  // dropped; the count keeps it (the host reports overflow)
   }
   if (reset && A.episode_log && (!compact || log_row >= 0)) {
     // reset_idx logging (:256-271): pre-reset sums, episode length, reached, goal distance
@@ -826,16 +679,9 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   if (reset) {
 #ifndef GO1_ABL_NO_RESET  // ablation build only: resets keep the state
     {
-      // the reset's uniforms (slots 0 .. 35 = Philox blocks 0 .. 8): lane sub16 < 9 of the env
-      // draws block sub16 (one evaluation per lane instead of one per draw), the env's lanes read
-      // them back from LDS (one wave per block: its LDS operations complete in order)
+      // the reset's uniforms (slots 0 .. 35 = Philox blocks 0 .. 8), staged through LDS
       __shared__ float s_ru[SEPB][GO1_RESET_SLOTS];
-      if (sub16 < GO1_RESET_SLOTS / 4) {
-        float uq[4];
-        rng.quad(sub16, uq);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s_ru[el][4 * sub16 + k] = uq[k];
-      }
+      rng_stage(rng, 0, GO1_RESET_SLOTS / 4, sub16, s_ru[el]);
       const float* ru = s_ru[el];
       auto u = [ru](int slot) { return ru[slot]; };
       reset_env(c, u, rng, eo_pre, leg, s_phys + LDS_DDP, root, q, qd, strength, offset, traj_new);
@@ -866,18 +712,12 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   float* oh = A.obs_history ? A.obs_history + (size_t)e * NO : nullptr;  // optional second copy
   const float clip = CI(clip_obs);
   // noise uniforms rng(47 + i) (:472-473): the env's observed noisy columns use slots 47 .. 49
-  // (gravity), 52 .. 63 (dof pos) and 64 .. 75 (dof vel), i.e. Philox blocks 11 .. 18: lane
-  // sub16 < 8 draws block 11 + sub16 into LDS (one evaluation per lane; it was two), and role
-  // r < 3 reads slots 52 + d and 64 + d, role 3 slots 47, 48, 49
+  // (gravity), 52 .. 63 (dof pos) and 64 .. 75 (dof vel), i.e. Philox blocks 11 .. 18, staged through
+  // LDS; role r < 3 reads slots 52 + d and 64 + d, role 3 slots 47, 48, 49
   const int dn = leg * 3 + (role < 3 ? role : 0);
   float un = 0.0f, uv = 0.0f, ug[3] = {0.0f, 0.0f, 0.0f};
   if (CI(add_noise)) {
-    if (sub16 < 8) {
-      float uq[4];
-      rng.quad(11 + sub16, uq);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s_u[el][4 * sub16 + k] = uq[k];
-    }
+    rng_stage(rng, 11, 8, sub16, s_u[el]);
     un = s_u[el][52 + dn - 44];
     uv = s_u[el][64 + dn - 44];
 #pragma unroll
@@ -1060,19 +900,7 @@ __global__ __launch_bounds__(TPB) void go1_reset_kernel(const go1_config* __rest
   const float eo[3] = {ter.env_origins[(size_t)e * 3], ter.env_origins[(size_t)e * 3 + 1],
                        ter.env_origins[(size_t)e * 3 + 2]};
   reset_env(c, rng, rng, eo, leg, c_gen->default_dof_pos, root, q, qd, strength, offset, traj);
-  const size_t d0 = (size_t)e * NDOF + leg * 3;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    st.dof_pos[d0 + j] = q[j];
-    st.dof_vel[d0 + j] = qd[j];
-    st.motor_strength[d0 + j] = strength[j];
-    st.motor_offset[d0 + j] = offset[j];
-    st.last_actions[d0 + j] = 0.0f;
-    st.last_dof_vel[d0 + j] = 0.0f;
-#pragma unroll
-    for (int k = 0; k < GO1_LAG_STEPS(c->decimation); ++k)
-      st.lag[(size_t)e * 12 * GO1_LAG_STEPS(c->decimation) + k * 12 + leg * 3 + j] = 0.0f;
-  }
+  joints_store_reset(st, e, leg, GO1_LAG_STEPS(c->decimation), q, qd, strength, offset);
   write_trajectory(c, rng, root, st.trajectory + (size_t)e * 6 * c->traj_length, leg, 4);
   st.feet_air_time[(size_t)e * 4 + leg] = 0.0f;  // (:248)
   const int ns = c->n_terms + 3;
@@ -1158,6 +986,18 @@ struct go1_handle {
 
 static thread_local std::string g_err;
 
+#define P(f, cols, dt) GO1_PLANE(go1_state, f, cols, GO1_DTYPE_##dt)
+static const PlaneRow STATE_PLANES[] = {
+    P(root, 13, F32), P(dof_pos, 12, F32), P(dof_vel, 12, F32), P(last_actions, 12, F32), P(last_dof_vel, 12, F32),
+    P(lag, 0, F32), P(pos_err_hist, 24, F32), P(vel_hist, 24, F32), P(motor_strength, 12, F32),
+    P(motor_offset, 12, F32), P(friction, 1, F32), P(restitution, 1, F32), P(payload, 1, F32),
+    P(episode_length, 1, I32), P(curr_pose_index, 1, I32), P(trajectory, 0, F32), P(base_rotation, 3, F32),
+    P(collision_count, 1, I32), P(episode_sums, 0, F32), P(joint_pos_target, 12, F32), P(feet_air_time, 4, F32),
+    P(last_contacts, 4, F32)};
+#undef P
+static_assert(sizeof(STATE_PLANES) / sizeof(STATE_PLANES[0]) == GO1_STATE_PLANES &&
+                  sizeof(go1_state) == GO1_STATE_PLANES * sizeof(void*), "go1_state planes");
+
 // the specialised kernel's values must match bit for bit (-0.0 and 0.0 are different constants)
 template <class T>
 static bool spec_eq(T a, T b) { return memcmp(&a, &b, sizeof(T)) == 0; }
@@ -1175,14 +1015,9 @@ static int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
+#define HIP_TRY(x) GO1_HIP_TRY(fail, x)
 // the library's other translation units (go1_terrain.hip) report through the same message
 int go1_internal_fail(int code, const std::string& msg) { return fail(code, msg); }
-
-#define HIP_TRY(x)                                                                      \
-  do {                                                                                  \
-    hipError_t _e = (x);                                                                \
-    if (_e != hipSuccess) return fail(GO1_E_HIP, std::string(#x ": ") + hipGetErrorString(_e)); \
-  } while (0)
 
 extern "C" {
 #ifdef GO1_STAMPS
@@ -1277,32 +1112,12 @@ int go1_create(const go1_config* cfg, go1_handle** out) {
 
 int go1_bind(go1_handle* h, const go1_state* s, const go1_plane* planes) {
   if (!h || !s || !planes) return fail(GO1_E_ARG, "go1_bind: null argument (state and plane descriptors required)");
-  const void* p[] = {s->root, s->dof_pos, s->dof_vel, s->last_actions, s->last_dof_vel, s->lag, s->pos_err_hist,
-                     s->vel_hist, s->motor_strength, s->motor_offset, s->friction, s->restitution, s->payload,
-                     s->episode_length, s->curr_pose_index, s->trajectory, s->base_rotation, s->collision_count,
-                     s->episode_sums, s->joint_pos_target, s->feet_air_time, s->last_contacts};
-  static_assert(sizeof(p) / sizeof(p[0]) == GO1_STATE_PLANES, "go1_state planes");
-  static const char* names[GO1_STATE_PLANES] = {
-      "root", "dof_pos", "dof_vel", "last_actions", "last_dof_vel", "lag", "pos_err_hist", "vel_hist",
-      "motor_strength", "motor_offset", "friction", "restitution", "payload", "episode_length",
-      "curr_pose_index", "trajectory", "base_rotation", "collision_count", "episode_sums", "joint_pos_target",
-      "feet_air_time", "last_contacts"};
-  const int64_t width[GO1_STATE_PLANES] = {13, 12, 12, 12, 12, 12 * GO1_LAG_STEPS(h->cfg.decimation), 24, 24, 12,
-                                           12, 1, 1, 1, 1, 1,
-                                           6 * (int64_t)h->cfg.traj_length, 3, 1, h->cfg.n_terms + 3, 12, 4, 4};
-  for (int i = 0; i < GO1_STATE_PLANES; ++i) {
-    const go1_plane& d = planes[i];
-    const int dt = (i == 13 || i == 14 || i == 17) ? GO1_DTYPE_I32 : GO1_DTYPE_F32;
-    if (!p[i]) return fail(GO1_E_ARG, std::string("go1_bind: state plane ") + names[i] + " is null");
-    if (d.rows != h->cfg.n_envs || d.cols != width[i] || d.dtype != dt)
-      return fail(GO1_E_ARG, std::string("go1_bind: state plane ") + names[i] + " must be (" +
-                                 std::to_string(h->cfg.n_envs) + ", " + std::to_string(width[i]) + ") " +
-                                 (dt == GO1_DTYPE_I32 ? "int32" : "float32"));
-    if (d.col_stride != 1 || (d.rows > 1 && d.row_stride != d.cols))
-      return fail(GO1_E_ARG, std::string("go1_bind: state plane ") + names[i] +
-                                 " is not dense row-major (strides " + std::to_string(d.row_stride) + ", " +
-                                 std::to_string(d.col_stride) + "): pass a contiguous tensor");
-  }
+  PlaneRow table[GO1_STATE_PLANES];
+  memcpy(table, STATE_PLANES, sizeof(table));
+  table[GO1_PLANE_INDEX(go1_state, lag)].cols = 12 * GO1_LAG_STEPS(h->cfg.decimation);
+  table[GO1_PLANE_INDEX(go1_state, trajectory)].cols = 6 * (int64_t)h->cfg.traj_length;
+  table[GO1_PLANE_INDEX(go1_state, episode_sums)].cols = h->cfg.n_terms + 3;
+  if (int rc = check_planes("go1_bind", s, table, planes, h->cfg.n_envs, fail)) return rc;
   h->st = *s;
   h->bound = true;
   return GO1_OK;
@@ -1346,14 +1161,7 @@ int go1_step(go1_handle* h, const go1_step_args* a, void* stream) {
   if (a->episode_log_count && (!a->episode_log || a->episode_log_cap < 0 || h->cfg.indefinite_slots))
     return fail(GO1_E_ARG, "go1_step: a compact episode log needs episode_log, a capacity >= 0 and no indefinite "
                            "reward slots (their bucket pass rewrites rows by env)");
-  // The optional event pair is attached to the kernel's own dispatch (hipExtLaunchKernelGGL: the
-  // events take the dispatch packet's start / end timestamps, as a profiler's kernel trace does),
-  // so ev_end - ev_begin is the kernel's duration without the queue work of separate event records.
-  hipEvent_t e0 = (hipEvent_t)a->ev_begin, e1 = (hipEvent_t)a->ev_end;
-  auto go = [&](auto kern) {
-    if (e0 || e1) hipExtLaunchKernelGGL(kern, grid, block, 0, s, e0, e1, 0, h->d_cfg, K);
-    else hipLaunchKernelGGL(kern, grid, block, 0, s, h->d_cfg, K);
-  };
+  auto go = [&](auto kern) { launch_timed(kern, grid, block, s, a->ev_begin, a->ev_end, h->d_cfg, K); };
   if (inj) {  // parity mode: the README configuration replays through the specialised kernel too
     if (full) go(go1_step_kernel<true, 15, false>);
     else if (h->spec) go(go1_step_kernel<true, 7, true>);
@@ -1371,7 +1179,7 @@ int go1_step(go1_handle* h, const go1_step_args* a, void* stream) {
                        a->reset, a->rew, a->episode_log);
     HIP_TRY(hipGetLastError());
   }
-h->prev_time_out = a->time_out;
+  h->prev_time_out = a->time_out;
   h->prev_extras = a->extras_time_outs;
   h->count++;
   return GO1_OK;

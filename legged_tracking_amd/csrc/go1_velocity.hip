@@ -17,6 +17,7 @@
 // transcendentals of the gait clock and the rewards via f64 (correctly rounded f32 but for rare double
 // roundings), so the results match oracle/vel_oracle.py to the ulp of numpy's own exp / sin / erf.
 #include "go1_device.h"
+#include "go1_step_shared.h"
 #include "../../include/go1_velocity.h"
 
 #include <algorithm>
@@ -191,7 +192,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   VCfg* __restrict__ v = (VCfg*)v_gen;
   const go1_vel_state& st = K.st;
   const go1_vel_step_args& A = K.a;
-  const int lane = threadIdx.x & 63, leg = lane & 3, lq = lane >> 4;
+  const int lane = threadIdx.x & 63, leg = lane & 3;
   const int role = lane >> 4, el = (lane >> 2) & 3, sub16 = 4 * role + leg;
   const bool owner = role == 0;
   const int e = blockIdx.x * SEPB + el;  // n % 16 == 0 (go1_vel_create)
@@ -201,12 +202,13 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   mlp_park(F, s_mlp, lane);
   const Rng rng = {A.uniforms, A.rng_seed, A.rng_step, e, e + c->env_id_offset, GO1_VEL_U_PER_ENV};
   const size_t d0 = (size_t)e * NDOF + leg * 3;
-  const int dec = c->decimation;
-  const float* lag_in = st.lag + (size_t)e * 12 * VLAG + leg * 3;
   const int NT = v->n_terms;
 
-  // ---------------- load
+  // ---------------- load (the per-joint registers; J: their view for the shared sub-step loop)
   float act[3], q[3], qd[3], eh[2][3], vh[2][3], strength[3], offset[3], dflt[3], tlim[3], lag_pre[VLAG][3];
+  float scaled[3], torque[3], tgt[3];
+  const Joints<VLAG> J = {act, q, qd, eh, vh, strength, offset, dflt, tlim, lag_pre, scaled, torque, tgt};
+  const float* lag_in = st.lag + (size_t)e * 12 * VLAG + leg * 3;
   float ldv[3], la[3], lla[3], ljpt[3], lljpt[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
@@ -253,126 +255,31 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     my_id[h] = k < NT ? v_gen->term_ids[k] : -1;
   }
   Phys P;
-  if (!INJ) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      P.pos[i] = st.root[(size_t)e * 13 + i];
-      P.wv[i] = f2{st.root[(size_t)e * 13 + 10 + i], st.root[(size_t)e * 13 + 7 + i]};
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) P.quat[i] = st.root[(size_t)e * 13 + 3 + i];
-  }
+  if (!INJ) phys_load_root(P, st.root + (size_t)e * 13);
   const Terr T = {nullptr, 0, 0, 1.0f, nullptr, 0, 0};  // the plane: floor z = 0, no ceiling
-  float scaled[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    scaled[j] = act[j] * c->action_scale;
-    if (j == 0) scaled[j] = scaled[j] * c->hip_scale_reduction;
-  }
 
   // ---------------- decimation loop (:76-82): lag ring pushed per sim step (:940-942)
-  float torque[3], tgt[3];
   float cf_raw[CF_RAW] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, cf_leg[9], cf_base[3], cf_hip[3];
-  for (int sub = 0; sub < dec; ++sub) {
-    {
-      const int m = 6 - sub;
-      const int back = m <= 0 ? 0 : (m + dec - 1) / dec;
-      float xin[3][6];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        float lg = scaled[j];
-#pragma unroll
-        for (int k = 0; k < VLAG; ++k) lg = back == VLAG - k ? lag_pre[k][j] : lg;
-        tgt[j] = lg + dflt[j];
-        const float err = q[j] - tgt[j] + offset[j];
-        xin[j][0] = err; xin[j][1] = eh[0][j]; xin[j][2] = eh[1][j];
-        xin[j][3] = qd[j]; xin[j][4] = vh[0][j]; xin[j][5] = vh[1][j];
-      }
-      float tq[3] = {0.0f, 0.0f, 0.0f}, b0[3], b1v[3];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const float* y = xin[j];
-        b0[j] = sel4(lq, y[0], y[1], y[2], y[3]);
-        b1v[j] = sel4(lq, y[4], y[5], 0.0f, 0.0f);
-      }
-      {
-        MlpFrag Fs;
-        mlp_unpark(Fs, s_mlp, lane);
-        mlp_group3(Fs, b0, b1v, tq);
-      }
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        eh[1][j] = eh[0][j];
-        eh[0][j] = xin[j][0];
-        vh[1][j] = vh[0][j];
-        vh[0][j] = qd[j];
-        torque[j] = clampf(tq[j] * strength[j], -tlim[j], tlim[j]);
-      }
-    }
-    if (INJ) {
-      const float* id = A.inj_dof + ((size_t)sub * c->n_envs + e) * NDOF * 2;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        q[j] = id[(leg * 3 + j) * 2];
-        qd[j] = id[(leg * 3 + j) * 2 + 1];
-      }
-    } else {
-      const float h = c->sim_dt / (float)c->n_internal;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) { P.q[j] = q[j]; P.qd[j] = qd[j]; }
-      for (int k = 0; k < c->n_internal; ++k) {
-        const bool last = (sub == dec - 1) && (k == c->n_internal - 1);
-        phys_substep(c, nullptr, P, torque, h, A.sim_gravity, friction, restitution, payload, T, leg, role, last,
-                     cf_raw, s_self[el], sub == 0 && k == 0);
-      }
-#pragma unroll
-      for (int j = 0; j < 3; ++j) { q[j] = P.q[j]; qd[j] = P.qd[j]; }
-    }
-    if (A.dbg_torques && owner) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) A.dbg_torques[((size_t)sub * c->n_envs + e) * NDOF + leg * 3 + j] = torque[j];
-    }
-  }
+  step_substeps<INJ>(c, A, J, P, s_mlp, nullptr, T, s_self[el], cf_raw, VLAG, friction, restitution, payload, e, lane,
+                     c->action_scale, c->hip_scale_reduction, leg, role);
   // the commands are first read by the post-physics (the gait clock): loaded here, not with the prologue, so
   // that they do not occupy 15 registers through the sub-steps (the self-collision narrow phase needs them)
   float cmd[GO1_VEL_NUM_COMMANDS];
 #pragma unroll
   for (int k = 0; k < GO1_VEL_NUM_COMMANDS; ++k) cmd[k] = st.commands[(size_t)e * GO1_VEL_NUM_COMMANDS + k];
   float root[13], fp[3], fv[3];
+  contact_totals<INJ>(cf_raw, A.inj_contact, e, leg, role, cf_leg, cf_base, cf_hip);
   if (INJ) {
 #pragma unroll
     for (int i = 0; i < 13; ++i) root[i] = A.inj_root[(size_t)e * 13 + i];
-    const float* ic = A.inj_contact + (size_t)e * NB * 3;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      cf_base[i] = ic[i];
-      cf_hip[i] = ic[(1 + leg * 4) * 3 + i];
-    }
-#pragma unroll
-    for (int b = 0; b < 3; ++b)
-#pragma unroll
-      for (int i = 0; i < 3; ++i) cf_leg[b * 3 + i] = ic[(2 + leg * 4 + b) * 3 + i];
     const float* ft = A.inj_feet + ((size_t)e * 4 + leg) * 6;
 #pragma unroll
     for (int i = 0; i < 3; ++i) { fp[i] = ft[i]; fv[i] = ft[3 + i]; }
   } else {
-    cf_sum(cf_raw, role, cf_leg, cf_base, cf_hip);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      root[i] = P.pos[i]; root[7 + i] = P.wv[i].y; root[10 + i] = P.wv[i].x;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) root[3 + i] = P.quat[i];
+    phys_store_root(P, root);
     foot_state(root, q, qd, leg, fp, fv);
   }
-  if (A.contact_forces && owner) {
-    float* o = A.contact_forces + (size_t)e * NB * 3;
-    if (leg == 0) { o[0] = cf_base[0]; o[1] = cf_base[1]; o[2] = cf_base[2]; }
-    float* ol = o + (1 + leg * 4) * 3;
-    ol[0] = cf_hip[0]; ol[1] = cf_hip[1]; ol[2] = cf_hip[2];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) ol[3 + i] = cf_leg[i];
-  }
+  if (A.contact_forces && owner) contact_store(A.contact_forces, e, leg, cf_leg, cf_base, cf_hip);
 
   // ================= post_physics_step (:108-154), contraction off =================
   const int ep = ep_in + 1;
@@ -412,18 +319,11 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     g[8 + leg] = desired;
   }
   // ---- DR every rand_interval (:714-717)
-  // slots 2 .. 14 = Philox blocks 0 .. 3: lane sub16 < 4 of the env draws block sub16 into LDS and the
-  // env's lanes read their slots back (one evaluation per lane instead of four in a row; one wave per
-  // block: its LDS operations complete in order)
+  // slots 2 .. 14 = Philox blocks 0 .. 3, staged through LDS (rng_stage)
   __shared__ float s_u[SEPB][48];
   const bool dr_step = ep % v->rand_interval == 0;
   if (dr_step) {
-    if (sub16 < 4) {
-      float uq[4];
-      rng.quad(sub16, uq);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s_u[el][4 * sub16 + k] = uq[k];
-    }
+    rng_stage(rng, 0, 4, sub16, s_u[el]);
     const float sv = s_u[el][GO1_VEL_U_DR] * v->strength_range + v->strength_lo;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
@@ -436,13 +336,8 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   bool reset = norm3_f(cf_base[0], cf_base[1], cf_base[2]) > 1.0f || time_out;
   if (v->use_terminal_body_height && root[2] < v->terminal_body_height) reset = true;
   bool diverged = false;
-  if (!INJ) {  // native-integrator divergence guard (go1_step.hip): the env is reset, its rewards zeroed
-    bool finite = true;
-#pragma unroll
-    for (int i = 0; i < 13; ++i) finite = finite & (fabsf(root[i]) < GO1_DIVERGED);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) finite = finite & (fabsf(q[j]) < GO1_DIVERGED) & (fabsf(qd[j]) < GO1_DIVERGED);
-    diverged = qsum(finite ? 0.0f : 1.0f) != 0.0f;
+  if (!INJ) {  // the env is reset, its rewards zeroed
+    diverged = state_diverged(root, q, qd);
     if (diverged) reset = true;
   }
 
@@ -612,30 +507,18 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   for (int j = 0; j < 3; ++j) { la_obs[j] = la[j]; }
   float gait_out = gait;
   if (A.episode_log_count) {
-    const uint64_t rmask = __ballot(reset && owner && leg == 0);
-    if (rmask != 0ull) {
-      int base = 0;
-      if (lane == 0) base = atomicAdd(A.episode_log_count, __popcll(rmask));
-      base = __shfl(base, 0);
-      const int row = base + __popcll(rmask & ((1ull << (4 * el)) - 1ull));
-      if (reset && A.episode_log_cap > 0) {  // a ring: the newest rows overwrite the oldest
-        float* lg = A.episode_log + (size_t)((uint32_t)row % (uint32_t)A.episode_log_cap) * (NE + 2);
+    const int row = wave_alloc_row(reset && owner && leg == 0, A.episode_log_count, lane, 4 * el);
+    if (reset && A.episode_log_cap > 0) {  // a ring: the newest rows overwrite the oldest
+      float* lg = A.episode_log + (size_t)((uint32_t)row % (uint32_t)A.episode_log_cap) * (NE + 2);
 #pragma unroll
-        for (int h = 0; h < 2; ++h)
-          if (sub16 + 16 * h < NE) lg[sub16 + 16 * h] = es[h];
-        if (sub16 == 0) { lg[NE] = __int_as_float(A.episode_log_tag); lg[NE + 1] = (float)e; }
-      }
+      for (int h = 0; h < 2; ++h)
+        if (sub16 + 16 * h < NE) lg[sub16 + 16 * h] = es[h];
+      if (sub16 == 0) { lg[NE] = __int_as_float(A.episode_log_tag); lg[NE + 1] = (float)e; }
     }
   }
   if (reset) {
     __shared__ float s_ru[SEPB][48];
-    // the reset's uniforms (slots 12 .. 59 = Philox blocks 3 .. 14): lane sub16 < 12 draws block 3 + sub16
-    if (sub16 < 12) {
-      float uq[4];
-      rng.quad(3 + sub16, uq);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s_ru[el][4 * sub16 + k] = uq[k];
-    }
+    rng_stage(rng, 3, 12, sub16, s_ru[el]);  // the reset's uniforms (slots 12 .. 59 = Philox blocks 3 .. 14)
     const float* ru = s_ru[el];
     auto u = [ru](int slot) { return ru[slot - 12]; };
     vel_reset_env(v, u, eo_pre, leg, root, q, qd, strength, offset);
@@ -667,15 +550,10 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   };
   auto noise = [&](float val, int i, float u) { return noisy ? val + (2.0f * u - 1.0f) * v->noise_vec[i] : val; };
   // the noisy columns' uniforms (gravity 0 .. 2, dof pos 18 .. 29, dof vel 30 .. 41: slots 47 .. 88 =
-  // Philox blocks 11 .. 22): lane sub16 < 12 draws block 11 + sub16 into LDS
+  // Philox blocks 11 .. 22), staged through LDS
   float uq = 0.0f, uv = 0.0f, ugr = 0.0f;
   if (noisy) {
-    if (sub16 < 12) {
-      float u4[4];
-      rng.quad(11 + sub16, u4);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s_u[el][4 * sub16 + k] = u4[k];
-    }
+    rng_stage(rng, 11, 12, sub16, s_u[el]);
     const int d = leg * 3 + (role < 3 ? role : 0);
     uq = s_u[el][GO1_VEL_U_NOISE + 18 + d - 44];
     uv = s_u[el][GO1_VEL_U_NOISE + 30 + d - 44];
@@ -837,19 +715,9 @@ __global__ __launch_bounds__(TPB) void go1_vel_reset_kernel(const go1_vel_config
   float root[13], q[3], qd[3], strength[3], offset[3];
   const float eo[3] = {env_origins[(size_t)e * 3], env_origins[(size_t)e * 3 + 1], env_origins[(size_t)e * 3 + 2]};
   vel_reset_env(v, rng, eo, leg, root, q, qd, strength, offset);
-  const size_t d0 = (size_t)e * NDOF + leg * 3;
+  joints_store_reset(st, e, leg, VLAG, q, qd, strength, offset);
 #pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    st.dof_pos[d0 + j] = q[j];
-    st.dof_vel[d0 + j] = qd[j];
-    st.motor_strength[d0 + j] = strength[j];
-    st.motor_offset[d0 + j] = offset[j];
-    st.last_actions[d0 + j] = 0.0f;
-    st.last_last_actions[d0 + j] = 0.0f;
-    st.last_dof_vel[d0 + j] = 0.0f;
-#pragma unroll
-    for (int k = 0; k < VLAG; ++k) st.lag[(size_t)e * 12 * VLAG + k * 12 + leg * 3 + j] = 0.0f;
-  }
+  for (int j = 0; j < 3; ++j) st.last_last_actions[(size_t)e * NDOF + leg * 3 + j] = 0.0f;
   if (leg == 0) {
 #pragma unroll
     for (int i = 0; i < 13; ++i) st.root[(size_t)e * 13 + i] = root[i];
@@ -1492,11 +1360,21 @@ static int vfail(int code, const std::string& msg) {
   g_verr = msg;
   return code;
 }
-#define VHIP_TRY(x)                                                                      \
-  do {                                                                                   \
-    hipError_t _e = (x);                                                                 \
-    if (_e != hipSuccess) return vfail(GO1_E_HIP, std::string(#x ": ") + hipGetErrorString(_e)); \
-  } while (0)
+#define VHIP_TRY(x) GO1_HIP_TRY(vfail, x)
+
+#define P(f, cols, dt) GO1_PLANE(go1_vel_state, f, cols, GO1_DTYPE_##dt)
+static const PlaneRow VEL_STATE_PLANES[] = {
+    P(root, 13, F32), P(dof_pos, 12, F32), P(dof_vel, 12, F32), P(last_actions, 12, F32), P(last_dof_vel, 12, F32),
+    P(lag, 12 * VLAG, F32), P(pos_err_hist, 24, F32), P(vel_hist, 24, F32), P(motor_strength, 12, F32),
+    P(motor_offset, 12, F32), P(friction, 1, F32), P(restitution, 1, F32), P(payload, 1, F32),
+    P(episode_length, 1, I32), P(last_last_actions, 12, F32), P(last_joint_pos_target, 12, F32),
+    P(last_last_joint_pos_target, 12, F32), P(commands, GO1_VEL_NUM_COMMANDS, F32), P(gait_indices, 1, F32),
+    P(last_contacts, 4, F32), P(command_sums, 0, F32), P(episode_sums, 0, F32), P(command_bins, 1, I32),
+    P(command_categories, 1, I32), {"curriculum_weights", offsetof(go1_vel_state, curriculum_weights), 0,
+                                    GO1_DTYPE_F64, GO1_VEL_N_CATEGORIES}};
+#undef P
+static_assert(sizeof(VEL_STATE_PLANES) / sizeof(VEL_STATE_PLANES[0]) == GO1_VEL_STATE_PLANES &&
+                  sizeof(go1_vel_state) == GO1_VEL_STATE_PLANES * sizeof(void*), "go1_vel_state planes");
 
 // curriculum workgroups: the per-env sampling splits over them (a 4096-env resample: 256 envs each)
 static int curriculum_blocks(int n) { return std::max(1, std::min(16, n / 256)); }
@@ -1601,35 +1479,12 @@ int go1_vel_create(const go1_config* cfg, const go1_vel_config* vel, const doubl
 
 int go1_vel_bind(go1_vel_handle* h, const go1_vel_state* s, const go1_plane* planes) {
   if (!h || !s || !planes) return vfail(GO1_E_ARG, "go1_vel_bind: null argument");
-  const void* p[] = {s->root, s->dof_pos, s->dof_vel, s->last_actions, s->last_dof_vel, s->lag, s->pos_err_hist,
-                     s->vel_hist, s->motor_strength, s->motor_offset, s->friction, s->restitution, s->payload,
-                     s->episode_length, s->last_last_actions, s->last_joint_pos_target,
-                     s->last_last_joint_pos_target, s->commands, s->gait_indices, s->last_contacts,
-                     s->command_sums, s->episode_sums, s->command_bins, s->command_categories,
-                     s->curriculum_weights};
-  static_assert(sizeof(p) / sizeof(p[0]) == GO1_VEL_STATE_PLANES, "go1_vel_state planes");
-  static const char* names[GO1_VEL_STATE_PLANES] = {
-      "root", "dof_pos", "dof_vel", "last_actions", "last_dof_vel", "lag", "pos_err_hist", "vel_hist",
-      "motor_strength", "motor_offset", "friction", "restitution", "payload", "episode_length",
-      "last_last_actions", "last_joint_pos_target", "last_last_joint_pos_target", "commands", "gait_indices",
-      "last_contacts", "command_sums", "episode_sums", "command_bins", "command_categories", "curriculum_weights"};
-  const int64_t nt = h->vcfg.n_terms, n = h->cfg.n_envs;
-  const int64_t width[GO1_VEL_STATE_PLANES] = {13, 12, 12, 12, 12, 12 * VLAG, 24, 24, 12, 12, 1, 1, 1, 1, 12, 12, 12,
-                                               GO1_VEL_NUM_COMMANDS, 1, 4, nt + GO1_VEL_SUM_EXTRA, nt + 1, 1, 1,
-                                               h->vcfg.n_bins};
-  for (int i = 0; i < GO1_VEL_STATE_PLANES; ++i) {
-    const go1_plane& d = planes[i];
-    const int dt = (i == 13 || i == 22 || i == 23) ? GO1_DTYPE_I32 : (i == 24 ? GO1_DTYPE_F64 : GO1_DTYPE_F32);
-    const int64_t rows = i == 24 ? GO1_VEL_N_CATEGORIES : n;
-    if (!p[i]) return vfail(GO1_E_ARG, std::string("go1_vel_bind: state plane ") + names[i] + " is null");
-    if (d.rows != rows || d.cols != width[i] || d.dtype != dt)
-      return vfail(GO1_E_ARG, std::string("go1_vel_bind: state plane ") + names[i] + " must be (" +
-                                  std::to_string(rows) + ", " + std::to_string(width[i]) + ") " +
-                                  (dt == GO1_DTYPE_I32 ? "int32" : (dt == GO1_DTYPE_F64 ? "float64" : "float32")));
-    if (d.col_stride != 1 || (d.rows > 1 && d.row_stride != d.cols))
-      return vfail(GO1_E_ARG, std::string("go1_vel_bind: state plane ") + names[i] +
-                                  " is not dense row-major: pass a contiguous tensor");
-  }
+  PlaneRow table[GO1_VEL_STATE_PLANES];
+  memcpy(table, VEL_STATE_PLANES, sizeof(table));
+  table[GO1_PLANE_INDEX(go1_vel_state, command_sums)].cols = h->vcfg.n_terms + GO1_VEL_SUM_EXTRA;
+  table[GO1_PLANE_INDEX(go1_vel_state, episode_sums)].cols = h->vcfg.n_terms + 1;
+  table[GO1_PLANE_INDEX(go1_vel_state, curriculum_weights)].cols = h->vcfg.n_bins;
+  if (int rc = check_planes("go1_vel_bind", s, table, planes, h->cfg.n_envs, vfail)) return rc;
   h->st = *s;
   h->bound = true;
   VHIP_TRY(hipMemset(h->d_cdf_ok, 0, GO1_VEL_N_CATEGORIES * sizeof(int32_t)));  // new weights plane
@@ -1691,10 +1546,8 @@ int go1_vel_step(go1_vel_handle* h, const go1_vel_step_args* a, void* stream) {
   C.hist_w = K.hist_w;
   C.hist_aligned = C.hist_w % 4 == 0 && ld_in % 4 == 0 && ld_out % 4 == 0 && ((uintptr_t)C.hist_in % 16) == 0 &&
                    ((uintptr_t)C.hist_out % 16) == 0;
-  hipEvent_t e0 = (hipEvent_t)a->ev_begin, e1 = (hipEvent_t)a->ev_end;
   auto go = [&](auto kern) {
-    if (e0 || e1) hipExtLaunchKernelGGL(kern, dim3(n / SEPB), dim3(TPB), 0, s, e0, e1, 0, h->d_cfg, h->d_vcfg, K);
-    else hipLaunchKernelGGL(kern, dim3(n / SEPB), dim3(TPB), 0, s, h->d_cfg, h->d_vcfg, K);
+    launch_timed(kern, dim3(n / SEPB), dim3(TPB), s, a->ev_begin, a->ev_end, h->d_cfg, h->d_vcfg, K);
   };
   if (inj) go(go1_vel_step_kernel<true>);
   else go(go1_vel_step_kernel<false>);

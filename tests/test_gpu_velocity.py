@@ -298,6 +298,25 @@ def test_vel_native_run_properties():
     env.env.close()
 
 
+def test_vel_bind_rejects_non_dense_or_mistyped_planes():
+    """go1_vel_bind checks every plane's shape, dtype and strides (go1_plane) against the same plane table
+    walk as go1_bind: a strided view or a wrong dtype (int32 and float64 planes included) is rejected at the
+    boundary, naming the plane.  Nothing is launched."""
+    n = 64
+    cfg, sim, P, names = make(n)
+    planes = dict(sim.state)
+    bad = dict(planes, root=torch.zeros((n, 26), device=DEV)[:, ::2])  # (n, 13) view, row stride 26
+    with pytest.raises(VEL.NativeError, match="root.*dense"):
+        sim.bind(bad)
+    bad = dict(planes, command_bins=torch.zeros((n, 1), device=DEV))  # float32 where int32 is required
+    with pytest.raises(VEL.NativeError, match="command_bins.*int32"):
+        sim.bind(bad)
+    bad = dict(planes, curriculum_weights=planes["curriculum_weights"].to(torch.float32))
+    with pytest.raises(VEL.NativeError, match="curriculum_weights.*float64"):
+        sim.bind(bad)
+    sim.bind(planes)  # the dense planes bind again
+
+
 def test_vel_runner_learns(tmp_path):
     """scripts/train_velocity_tracking.py's loop (Runner.learn, ppo_cse/__init__.py) over the HIP velocity env:
     rollout with the 30-deep history (2100 inputs, streamed through the fused policy kernel in chunks of

@@ -1,6 +1,6 @@
 """Every diagnostic build of the step kernels still compiles (no GPU needed).
 
-go1_step.hip (with the device code it shares with the velocity step, go1_device.h) keeps two kinds of compile-time switches, both measurement instrumentation, never
+go1_step.hip (with the device code it shares with the velocity step, go1_device.h and go1_step_shared.h) keeps two kinds of compile-time switches, both measurement instrumentation, never
 shipped: the ablation builds of tools/abl_kernel.sh (GO1_ABL_*: a section of the kernel compiled
 out, to price it in situ) and the timing / accounting builds (GO1_STAMPS: s_memtime stamps for
 tools/stamps.py; GO1_ISA_MARKS: section markers for tools/isa_sections.py).  Variants that were
@@ -18,7 +18,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "legged_tracking_amd", "csrc")
 SRC = os.path.join(CSRC, "go1_step.hip")
-SCANNED = [SRC, os.path.join(CSRC, "go1_device.h")]
+SCANNED = [SRC, os.path.join(CSRC, "go1_device.h"), os.path.join(CSRC, "go1_step_shared.h")]
 VEL_SRC = os.path.join(CSRC, "go1_velocity.hip")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 

@@ -59,7 +59,7 @@ def main():
     g.close()
 
     name = {}
-    for f in ("go1_step.hip", "go1_device.h"):  # (a line number marked in both files names both)
+    for f in ("go1_step.hip", "go1_device.h", "go1_step_shared.h"):  # (a line number marked in several files names them all)
         src = open(os.path.join(ROOT, "legged_tracking_amd", "csrc", f)).read().splitlines()
         for i, l in enumerate(src):
             m = re.search(r"MARK\((\w+)\)", l)
