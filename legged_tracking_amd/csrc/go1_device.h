@@ -11,6 +11,7 @@
 
 #include <new>
 #include <string>
+#include <type_traits>
 
 #include "../../include/go1_mi355x.h"
 #include "go1_model_consts.h"
@@ -178,6 +179,43 @@ __device__ __forceinline__ void pairsum_rows_n(const float* v, float* lo, float*
     lo[i] = __uint_as_float(r[0]);
     hi[i] = __uint_as_float(r[1]);
   }
+}
+
+// Role "sums" of values that only some rows hold.  v_permlane16_swap(v, v) returns (rows 0 0 2 2, rows 1 1 3 3) of
+// v: its second output already carries the odd rows, so these take no select to zero the other rows and no add of
+// those zeros (x + 0 = x; only a -0 keeps its sign here, where 0 + -0 gave +0).
+// N values of row 1 onto every lane: one v_permlane32_swap spreads the second output's rows 0-1.
+template <int N>
+__device__ __forceinline__ void row1_bcast_n(const float* v, float* out) {
+  float b[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i]), false, false);
+    b[i] = __uint_as_float(r[1]);
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(b[i]), __float_as_uint(b[i]), false, false);
+    out[i] = __uint_as_float(r[0]);
+  }
+}
+// N sums row 1 + row 3 on every lane (rowsum4_n's order with rows 0 and 2 zero)
+template <int N>
+__device__ __forceinline__ void oddrows_sum_n(float* v) {
+  float a[N], b[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i]), false, false);
+    b[i] = __uint_as_float(r[1]);
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(b[i]), __float_as_uint(b[i]), false, false);
+    a[i] = __uint_as_float(r[0]);
+    b[i] = __uint_as_float(r[1]);
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = a[i] + b[i];
 }
 
 // ---------------------------------------------------------------- actuator net
@@ -1543,10 +1581,15 @@ __device__ __forceinline__ float rsum(float v) { return rowsum4(v); }
 // the lane's own primitive into this env's LDS scratch; rb: the radius of its bounding sphere about the segment's middle
 // (half the segment plus r), for the narrow phase's first test
 __device__ __forceinline__ void self_put(float* sc, int leg, int role, const float* P0, const float* P1, float r,
-                                         float rb, const float* V0, const float* V1) {
+                                         float rb) {
   float4* Q = reinterpret_cast<float4*>(sc) + 4 * (4 * leg + role);
   Q[0] = make_float4(P0[0], P0[1], P0[2], r);
   Q[1] = make_float4(P1[0], P1[1], P1[2], rb);
+}
+// the velocity half of the record: only the spring of a touching pair reads it, so it is written (by every lane of
+// the wave, on a wave-uniform condition) when the first pair of the sub-step touches -- one entering wave in ten
+__device__ __forceinline__ void self_put_vel(float* sc, int leg, int role, const float* V0, const float* V1) {
+  float4* Q = reinterpret_cast<float4*>(sc) + 4 * (4 * leg + role);
   Q[2] = make_float4(V0[0], V0[1], V0[2], 0.0f);
   Q[3] = make_float4(V1[0], V1[1], V1[2], 0.0f);
 }
@@ -1615,8 +1658,10 @@ __device__ __forceinline__ float seg_box_t(const float* P0, const float* P1, con
 // index), spheres of the two radii at the closest points s (on A), t (on B); the force on A, or its negative on B
 // (own_first false), and the own primitive's point (world).  A, B: (P0 r, P1, V0, V1) records in LDS, so the two
 // lanes of a pair compute the same bits and apply exactly opposite forces.
-__device__ __forceinline__ void self_pair_force(const float4* A, const float4* B, bool own_first, float ks, float ds,
-                                                float* F, float* pown, bool& touch) {
+// need_vel: called (wave-uniformly) before the velocity records are read.
+template <class NV>
+__device__ __forceinline__ void self_pair_force(const float4* A, const float4* B, bool own_first, bool act, float ks,
+                                                float ds, float* F, float* pown, bool& touch, NV need_vel) {
   const float4 a0 = A[0], a1 = A[1], b0 = B[0], b1 = B[1];
   const float pa0[3] = {a0.x, a0.y, a0.z}, da[3] = {a1.x - a0.x, a1.y - a0.y, a1.z - a0.z};
   const float pb0[3] = {b0.x, b0.y, b0.z}, db[3] = {b1.x - b0.x, b1.y - b0.y, b1.z - b0.z};
@@ -1628,10 +1673,13 @@ __device__ __forceinline__ void self_pair_force(const float4* A, const float4* B
   const float dd = d0 * d0 + d1 * d1 + d2 * d2, rs = a0.w + b0.w;
 #pragma unroll
   for (int i = 0; i < 3; ++i) { pown[i] = own_first ? pa[i] : pb[i]; F[i] = 0.0f; }
-  touch = dd < rs * rs;
+  // act: the lane has a pair this trip (an idle lane is handed its own leg's primitive 0 -- for a thigh lane itself,
+  // at distance 0 -- and must not count as touching)
+  touch = act & (dd < rs * rs);
   // the spring only where some lane of the wave has an overlap (most pairs the boxes let through do not touch; a
   // pair that does not has no force, so skipping it changes nothing)
   if (!__any(touch)) return;
+  need_vel();
   const float inv = dd > 1e-18f ? frsq(dd) : 0.0f;
   const float n0 = dd > 1e-18f ? d0 * inv : 0.0f, n1 = dd > 1e-18f ? d1 * inv : 0.0f, n2 = dd > 1e-18f ? d2 * inv : 1.0f;
   const float pen = rs - dd * inv;
@@ -1709,18 +1757,32 @@ __device__ __forceinline__ int quad_or(int v) {
 
 // Narrow phase (a wave whose broad phase found a candidate).  sc: this env's LDS scratch, the primitives already
 // written (self_put).  Each lane sums the forces on its own primitive from its candidate partners: per candidate
-// partner leg (a per-lane list walked with ctz: the loop runs as often as the lane with the most candidates needs),
-// the leg's four primitives (the own leg's two-joints-apart ones for d = 0), each pair evaluated in its canonical
+// partner leg (tested where some lane of the wave has that partner; own_lo, own_hi: the own primitive's world box),
+// the leg's four primitives (the own leg's two-joints-apart ones for d = 0) into a per-lane work list walked with
+// ctz (the pair loop runs as often as the lane with the longest list needs), each pair evaluated in its canonical
 // order (the lower primitive index first), so the two lanes of a pair compute the same bits and apply exactly
 // opposite forces, every sum in a fixed order.  Then the trunk box for a folded leg.  Output: the world force Fo on
 // the own primitive and its moment Mo about the own body's origin pb; wb: the trunk reaction of the lane's box
-// contact (base frame).
+// contact (base frame).  vel(V0, V1): the velocities of the own primitive's ends (world), computed only in a wave
+// and a sub-step that reads them -- a touching pair (then every lane writes its record first) or a box contact.
+template <class VF>
 __device__ __forceinline__ void self_narrow(CCfg* __restrict__ cfg, float* sc, int leg, int role, int mask,
                                            const float* R, const float* pos, const float* vb, const float* th,
-                                           const float* pb, float* Fo, float* Mo, float* wb) {
+                                           const float* pb, const float* own_lo, const float* own_hi, float* Fo,
+                                           float* Mo, float* wb, VF vel) {
   const float ks = cfg->self_stiffness, ds = cfg->self_damping;
   const float4* Pr = reinterpret_cast<const float4*>(sc);
   const int io = 4 * leg + role;
+  bool vel_put = false;  // wave-uniform: the velocity records of this sub-step are in LDS
+  auto need_vel = [&]() {
+    if (!vel_put) {
+      float V0[3], V1[3];
+      vel(V0, V1);
+      self_put_vel(sc, leg, role, V0, V1);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the other lanes' records, as after self_put
+      vel_put = true;
+    }
+  };
   const int lp1 = (leg >> 1) ? 5 : 0, lp2 = (leg & 1) ? 4 : 1, lp3 = (leg == 0 || leg == 3) ? 2 : 3;
   // candidate partner legs, bit d: leg ^ d (d = 0: the own leg's links two joints apart, when folded)
   unsigned cand = ((mask >> (10 + leg)) & 1) | (((mask >> lp1) & 1) << 1) | (((mask >> lp2) & 1) << 2) |
@@ -1734,42 +1796,53 @@ __device__ __forceinline__ void self_narrow(CCfg* __restrict__ cfg, float* sc, i
     Mo[1] += p2 * F[0] - p0 * F[2];
     Mo[2] += p0 * F[1] - p1 * F[0];
   };
-  // first the bounding boxes (the segment's ends grown by the radius, world axes) of the candidate legs' primitives,
-  // all four partners' loads in one LDS round trip, into a per-lane work list (bit 4 d + m: primitive m of leg ^ d);
-  // then the pairs of the list -- both loops run as often as the busiest lane needs
+  // first the bounding boxes (the segment's ends grown by the radius, world axes) of the candidate legs' primitives
+  // into a per-lane work list (bit 4 d + m: primitive m of leg ^ d), then the pairs of the list.  The boxes travel
+  // in registers: every lane holds its own, the row swaps hand it the four roles' boxes of its leg, and per partner
+  // leg d that some lane of the wave has as a candidate (wave-uniform) a DPP quad_perm fetches leg ^ d's -- no LDS
+  // round trip, the same boxes and the same list as from the records
   unsigned work = 0u;
   {
-    const float4 O0 = Pr[4 * io], O1 = Pr[4 * io + 1];
-    const float olx = fminf(O0.x, O1.x) - O0.w, ohx = fmaxf(O0.x, O1.x) + O0.w;
-    const float oly = fminf(O0.y, O1.y) - O0.w, ohy = fmaxf(O0.y, O1.y) + O0.w;
-    const float olz = fminf(O0.z, O1.z) - O0.w, ohz = fmaxf(O0.z, O1.z) + O0.w;
 #ifdef GO1_ABL_NO_TESTLOOP  // ablation build only: no partner tests (and so no pairs)
     cand = 0u;
 #endif
 #ifdef GO1_ABL_RT_NO_TESTLOOP  // ablation build only: the same, decided at run time (the code stays)
     cand = cfg->self_stiffness > 1e30f ? cand : 0u;
 #endif
-    while (__any(cand != 0u)) {
-      const bool act = cand != 0u;
-      const int d = act ? __builtin_ctz(cand) : 0;
-      cand &= cand - 1u;
-      const unsigned keep = !act ? 0u : (d == 0 ? keep_same : 0xFu);
-      const float4* Q = Pr + 16 * (leg ^ d);
-      float4 B0[4], B1[4];
+    float rbx[4][6];  // (lo xyz, hi xyz) of primitive m of the own leg
 #pragma unroll
-      for (int m = 0; m < 4; ++m) { B0[m] = Q[4 * m]; B1[m] = Q[4 * m + 1]; }
-      __builtin_amdgcn_sched_barrier(0);
+    for (int k = 0; k < 6; ++k) {
+      const uint32_t v = __float_as_uint(k < 3 ? own_lo[k] : own_hi[k - 3]);
+      auto a = __builtin_amdgcn_permlane16_swap(v, v, false, false);        // rows (0 0 2 2), (1 1 3 3)
+      auto e = __builtin_amdgcn_permlane32_swap(a[0], a[0], false, false);  // row 0, row 2 on every lane
+      auto o = __builtin_amdgcn_permlane32_swap(a[1], a[1], false, false);  // row 1, row 3
+      rbx[0][k] = __uint_as_float(e[0]); rbx[2][k] = __uint_as_float(e[1]);
+      rbx[1][k] = __uint_as_float(o[0]); rbx[3][k] = __uint_as_float(o[1]);
+    }
+    auto test = [&](auto dtag) {
+      constexpr int D = decltype(dtag)::value;
+      if (!__any((cand >> D) & 1u)) return;
       unsigned bits = 0u;
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
-        const float r = B0[m].w;
-        const bool ox = (fminf(B0[m].x, B1[m].x) - r <= ohx) & (olx <= fmaxf(B0[m].x, B1[m].x) + r);
-        const bool oy = (fminf(B0[m].y, B1[m].y) - r <= ohy) & (oly <= fmaxf(B0[m].y, B1[m].y) + r);
-        const bool oz = (fminf(B0[m].z, B1[m].z) - r <= ohz) & (olz <= fmaxf(B0[m].z, B1[m].z) + r);
+        float q[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          if constexpr (D == 0) q[k] = rbx[m][k];
+          else q[k] = quad_xor<D>(rbx[m][k]);
+        }
+        const bool ox = (q[0] <= own_hi[0]) & (own_lo[0] <= q[3]);
+        const bool oy = (q[1] <= own_hi[1]) & (own_lo[1] <= q[4]);
+        const bool oz = (q[2] <= own_hi[2]) & (own_lo[2] <= q[5]);
         bits |= (ox & oy & oz) ? 1u << m : 0u;
       }
-      work |= (bits & keep) << (4 * d);
-    }
+      const unsigned keep = ((cand >> D) & 1u) ? (D == 0 ? keep_same : 0xFu) : 0u;
+      work |= (bits & keep) << (4 * D);
+    };
+    test(std::integral_constant<int, 0>{});
+    test(std::integral_constant<int, 1>{});
+    test(std::integral_constant<int, 2>{});
+    test(std::integral_constant<int, 3>{});
   }
   MARK(self_tests_done);
 #ifdef GO1_ABL_NO_PAIRLOOP  // ablation build only: the pairs tested but never evaluated
@@ -1786,8 +1859,8 @@ __device__ __forceinline__ void self_narrow(CCfg* __restrict__ cfg, float* sc, i
     const bool first = io < ip;
     float F[3], p[3];
     bool touch;
-    self_pair_force(Pr + 4 * min(io, ip), Pr + 4 * max(io, ip), first, ks, ds, F, p, touch);
-    if (__any(act & touch)) {
+    self_pair_force(Pr + 4 * min(io, ip), Pr + 4 * max(io, ip), first, act, ks, ds, F, p, touch, need_vel);
+    if (__any(touch)) {
       const float Fw[3] = {act ? F[0] : 0.0f, act ? F[1] : 0.0f, act ? F[2] : 0.0f};
       acc(p, Fw);
     }
@@ -1796,12 +1869,16 @@ __device__ __forceinline__ void self_narrow(CCfg* __restrict__ cfg, float* sc, i
   // the trunk box, for a folded leg's thigh, calf and foot (the hip is the trunk's neighbour) whose segment's
   // trunk-frame AABB, grown by its radius, meets the box (the fold gate is coarse: most folded links are far from
   // the trunk, and a link that misses the grown box has no force -- skipping it changes nothing)
-  const float4 O0 = Pr[4 * io], O1 = Pr[4 * io + 1];
 #ifdef GO1_ABL_NO_BOXPHASE  // ablation build only: no capsule-box pairs
   bool on = false;
 #else
   bool on = ((mask >> (6 + leg)) & 1) & (role != 1);
 #endif
+  if (!__any(on)) {  // no folded leg in the wave (the workload's every wave): not even the transform below
+    MARK(self_box_done);
+    return;
+  }
+  const float4 O0 = Pr[4 * io], O1 = Pr[4 * io + 1];
   {
     const float w0[3] = {O0.x - pos[0], O0.y - pos[1], O0.z - pos[2]}, w1[3] = {O1.x - pos[0], O1.y - pos[1], O1.z - pos[2]};
 #pragma unroll
@@ -1812,7 +1889,10 @@ __device__ __forceinline__ void self_narrow(CCfg* __restrict__ cfg, float* sc, i
     }
   }
   if (__any(on)) {
-    const float4 O2 = Pr[4 * io + 2], O3 = Pr[4 * io + 3];
+    // the own ends' velocities from registers (the same bits as the record a touching pair may have written)
+    float V0[3], V1[3];
+    vel(V0, V1);
+    const float4 O2 = make_float4(V0[0], V0[1], V0[2], 0.0f), O3 = make_float4(V1[0], V1[1], V1[2], 0.0f);
     const float P0[3] = {O0.x, O0.y, O0.z}, P1[3] = {O1.x, O1.y, O1.z};
     const float u = role == 3 ? 0.0f : seg_box_t(P0, P1, R, pos, th);
     const float4 C = make_float4(O0.x + u * (O1.x - O0.x), O0.y + u * (O1.y - O0.y), O0.z + u * (O1.z - O0.z), O0.w);
@@ -2069,36 +2149,47 @@ __device__ __forceinline__ void phys_substep(CCfg* __restrict__ cfg, const float
     if (__any(mask != 0)) {
 #endif
       // the lane's own primitive (its x half's link): the whole segment, ends and their velocities (world)
-      float P0[3], P1[3], V0[3], V1[3];
+      float P0[3], P1[3];
+      f2 e[3];  // (end 0, end 1) in the link frame
       {
         const float* kn = origin + 6;
-        f2 e[3];  // (end 0, end 1) in the link frame
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
           const float hy0 = i == 1 ? msy * hip_y0 : 0.0f, hy1 = i == 1 ? msy * hip_y1 : 0.0f;
           e[i] = f2{sel4(role, 0.0f, hy0, 0.0f, foot[i]), sel4(role, kn[i], hy1, foot[i], foot[i])};
         }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          const f2 p = ps[i].x + Rs[3 * i].x * e[0] + Rs[3 * i + 1].x * e[1] + Rs[3 * i + 2].x * e[2];
+          P0[i] = p.x; P1[i] = p.y;
+        }
+      }
+      // the ends' velocities, for self_narrow where it reads them (a touching pair, a box contact)
+      auto vel = [&](float* V0, float* V1) {
         const float w[3] = {vs[0].x, vs[1].x, vs[2].x};
         const f2 wl[3] = {w[1] * e[2] - w[2] * e[1], w[2] * e[0] - w[0] * e[2], w[0] * e[1] - w[1] * e[0]};
         const f2 vlin[3] = {vs[3].x + wl[0], vs[4].x + wl[1], vs[5].x + wl[2]};
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-          const f2 p = ps[i].x + Rs[3 * i].x * e[0] + Rs[3 * i + 1].x * e[1] + Rs[3 * i + 2].x * e[2];
           const f2 v = Rs[3 * i].x * vlin[0] + Rs[3 * i + 1].x * vlin[1] + Rs[3 * i + 2].x * vlin[2];
-          P0[i] = p.x; P1[i] = p.y; V0[i] = v.x; V1[i] = v.y;
+          V0[i] = v.x; V1[i] = v.y;
         }
-      }
+      };
       // bounding radius: half the link's segment (thigh, calf: half the knee / foot offset; hip: half the capsule's
       // segment; foot: a point) plus its radius
       const float half = sel4(role, 0.5f * fabsf(origin[8]), 0.5f * (hip_y1 - hip_y0), 0.5f * fabsf(foot[2]), 0.0f);
-      self_put(self_sc, leg, role, P0, P1, rr.x, half + rr.x, V0, V1);
+      self_put(self_sc, leg, role, P0, P1, rr.x, half + rr.x);
       // the block is this one wave (TPB 64): the other lanes' primitives are visible once the wave's own LDS
       // writes completed -- no s_barrier, and above all no vmcnt(0) drain of the terrain loads in flight
       static_assert(TPB == 64, "self-collision LDS exchange assumes one wave per block");
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       MARK(self_put_done);
       const float pb[3] = {ps[0].x, ps[1].x, ps[2].x};
-      self_narrow(cfg, self_sc, leg, role, mask, R, S.pos, vb, th, pb, Fo, Mo, wb);
+      // the own primitive's world-axis box (its segment's ends grown by its radius), for the partner tests
+      float own_lo[3], own_hi[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { own_lo[i] = fminf(P0[i], P1[i]) - rr.x; own_hi[i] = fmaxf(P0[i], P1[i]) + rr.x; }
+      self_narrow(cfg, self_sc, leg, role, mask, R, S.pos, vb, th, pb, own_lo, own_hi, Fo, Mo, wb, vel);
       // the next sub-step's self_put must not overtake this one's partner reads of other lanes' records
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       MARK(self_narrow_done);
@@ -2274,11 +2365,11 @@ __device__ __forceinline__ void phys_substep(CCfg* __restrict__ cfg, const float
 #pragma unroll
       for (int i = 0; i < 9; ++i) { ci_th.b[i] = th6[18 + i]; ci_ca.b[i] = ca6[18 + i]; }
     }
-    {  // the hip capsule (row 1's x half): the rows 0-1 sum of a value that only row 1 holds
-      float hp[6 + 21], lo[6 + 21], hi[6 + 21];
+    {  // the hip capsule (row 1's x half): a value that only row 1 holds, handed to every lane
+      float hp[6 + 21], lo[6 + 21];
 #pragma unroll
-      for (int k = 0; k < 27; ++k) hp[k] = hip_lane ? term(0, k) : 0.0f;
-      pairsum_rows_n<6 + 21>(hp, lo, hi);
+      for (int k = 0; k < 27; ++k) hp[k] = term(0, k);
+      row1_bcast_n<6 + 21>(hp, lo);
 #pragma unroll
       for (int i = 0; i < 3; ++i) pAp[0][i] -= f2{lo[i], lo[3 + i]};
 #pragma unroll
@@ -2287,10 +2378,12 @@ __device__ __forceinline__ void phys_substep(CCfg* __restrict__ cfg, const float
       for (int i = 0; i < 9; ++i) ci_hp.b[i] = lo[18 + i];
     }
     {  // the trunk: this leg's corners (odd rows' y halves) and the box reactions
+      // (the 21 added-mass values on rows 1 and 3 only: the odd rows' sum; the six forces on every row)
       float bs[6 + 21];
 #pragma unroll
-      for (int k = 0; k < 27; ++k) bs[k] = k < 6 ? fbase[k] : (even ? 0.0f : term(1, k));
-      rowsum4_n<6 + 21>(bs);
+      for (int k = 0; k < 27; ++k) bs[k] = k < 6 ? fbase[k] : term(1, k);
+      rowsum4_n<6>(bs);
+      oddrows_sum_n<21>(bs + 6);
 #pragma unroll
       for (int i = 0; i < 6; ++i) fbase[i] = bs[i];
 #pragma unroll
