@@ -92,7 +92,7 @@ class Go1State(C.Structure):
 
 
 GO1_STATE_PLANES = 22
-GO1_DTYPE_F32, GO1_DTYPE_I32 = 0, 1
+GO1_DTYPE_F32, GO1_DTYPE_I32, GO1_DTYPE_F64 = 0, 1, 2
 
 
 class Go1Plane(C.Structure):
@@ -101,16 +101,18 @@ class Go1Plane(C.Structure):
                 ("dtype", I32), ("pad", I32)]
 
 
-def plane_descs(tensors):
-    """go1_plane[GO1_STATE_PLANES] for a {name: tensor} state, in go1_state order (torch shapes /
-    strides as they are: go1_bind, not this helper, decides what it accepts)."""
-    arr = (Go1Plane * GO1_STATE_PLANES)()
-    for i, (name, _) in enumerate(Go1State._fields_):
+def plane_descs(fields, tensors):
+    """go1_plane[len(fields)] for a {name: tensor} state, in the order of `fields` (the _fields_ of
+    Go1State or vel_abi.Go1VelState); f32, i32 and f64 planes, torch shapes / strides as they are:
+    the library's bind, not this helper, decides what it accepts."""
+    dtypes = {"torch.int32": GO1_DTYPE_I32, "torch.float64": GO1_DTYPE_F64}
+    arr = (Go1Plane * len(fields))()
+    for i, (name, _) in enumerate(fields):
         t = tensors[name]
         shape = tuple(t.shape) + (1,) * (2 - t.dim())
         stride = tuple(t.stride()) + (1,) * (2 - t.dim())
         arr[i] = Go1Plane(rows=shape[0], cols=shape[1], row_stride=stride[0], col_stride=stride[1],
-                          dtype=GO1_DTYPE_I32 if str(t.dtype) == "torch.int32" else GO1_DTYPE_F32)
+                          dtype=dtypes.get(str(t.dtype), GO1_DTYPE_F32))
     return arr
 
 

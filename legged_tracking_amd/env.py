@@ -33,61 +33,15 @@ Differences from the reference, all documented in DESIGN.md:
   * eval envs (eval_cfg), curriculum (cl_fix_target), push_robots and
     randomize_rigids_after_start are not on this path and raise.
 """
-import math
 from collections import defaultdict, deque
 
 import numpy as np
 import torch
 
-from . import abi, config as CF, layout as L, terrain as T
+from . import abi, config as CF, terrain as T
+from .env_base import OUT_RING, EnvBase, StepExtras  # noqa: F401  (OUT_RING, StepExtras: importable from here)
 
-OUT_RING = 4
 EPISODE_RING = 64  # steps per half of the episode-log ring (fewer for very large n_envs)
-_LAZY = object()
-
-
-def _dist_info():
-    try:
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized():
-            return dist.get_rank(), dist.get_world_size()
-    except Exception:
-        pass
-    return 0, 1
-
-
-class StepExtras(dict):
-    """The env's `extras` dict: device-backed entries are materialised on read."""
-
-    def __init__(self, env):
-        super().__init__()
-        self._env = env
-        self._lazy = {}
-
-    def set_lazy(self, key, fn):
-        self._lazy[key] = fn
-        dict.__setitem__(self, key, _LAZY)
-
-    def __getitem__(self, key):
-        if key in ("train/episode", "eval/episode", "timeouts"):
-            self._env._flush_episode_log()
-        v = dict.__getitem__(self, key)
-        return self._lazy[key]() if v is _LAZY else v
-
-    def get(self, key, default=None):
-        return self[key] if key in self else default
-
-    def deferred_time_outs(self):
-        """extras["time_outs"] with its pending rebinding left to the consumer: returns
-        (tensor, (flag, pending, dst) device pointers or None).  The PPO record kernel resolves
-        it (rollout.py PPO.process_env_step), saving the sync launch a plain read costs."""
-        return self._env._deferred_time_outs()
-
-    def items(self):
-        return [(k, self[k]) for k in list(self.keys())]
-
-    def values(self):
-        return [self[k] for k in list(self.keys())]
 
 
 class EpisodeLogRing:
@@ -302,7 +256,7 @@ def _episode_dicts():
     return defaultdict(lambda: deque([], 4000)), defaultdict(lambda: deque([], 4000)), deque([], 4000)
 
 
-class LeggedRobot:
+class LeggedRobot(EnvBase):
     """LeggedRobot (:24-362) for the README configuration, backed by the HIP step."""
 
     def __init__(self, cfg, sim_params=None, physics_engine="SIM_PHYSX", sim_device="cuda:0", headless=True,
@@ -315,33 +269,15 @@ class LeggedRobot:
         dr = cfg.domain_rand
         if getattr(dr, "push_robots", False) or getattr(dr, "randomize_rigids_after_start", False):
             raise NotImplementedError("push_robots / randomize_rigids_after_start are not on the accelerated path")
-        self.cfg = cfg
-        self.eval_cfg = None
-        self.sim_device = sim_device
-        self.headless = headless
-        if rank is None or world_size is None:
-            r, w = _dist_info()
-            rank = r if rank is None else rank
-            world_size = w if world_size is None else world_size
-        self.rank, self.world_size = rank, world_size
-        self.num_obs = cfg.env.num_observations
-        self.num_privileged_obs = cfg.env.num_privileged_obs
-        self.num_actions = cfg.env.num_actions
-        self.num_envs = self.num_train_envs = cfg.env.num_envs
-        self.num_eval_envs = 0
-        self.seed = int(seed)
         d = CF.derived(cfg)
-        self.dt = d["dt"]
+        self._init_dims(cfg, d, sim_device, headless, seed, rank, world_size)
+        rank = self.rank
         self.max_episode_length_s = cfg.env.episode_length_s
-        self.max_episode_length = d["max_episode_length"]
-        self.reward_scales = dict(d["reward_scales"])
         # reward slots in Cfg.reward_scales order (the C ABI's term table; unknown terms raise in
         # build_abi_config, terms the container lacks keep a zero sum as in the reference :1390-1395)
         self.reward_names = list(self.reward_scales)
         self.sum_keys = tuple(self.reward_names) + ("total", "total_pos", "total_neg")
-        self._gravity_interval = d["gravity_rand_interval"]
-        self._gravity_duration = d["gravity_rand_duration"]
-        n, n_global = self.num_envs, self.num_envs * world_size
+        n, n_global = self.num_envs, self._n_global
         self._abi_cfg = CF.build_abi_config(cfg, n_envs=n, physics=physics)
         self._abi_cfg.env_id_offset = rank * n
         # terrain: the global grid is built identically on every rank (same seed), each
@@ -361,15 +297,8 @@ class LeggedRobot:
         self._sim.set_terrain(td.tiles, td.env_tile[sl], td.env_terrain_origin[sl], td.env_origins[sl])
         self.env_origins = torch.as_tensor(td.env_origins[sl], device=self.device)
         dev = self.device
-        # output rings
-        self._obs = torch.zeros((OUT_RING, n, self.num_obs), device=dev)
+        self._init_host_state()
         self._obs_hist = None  # ring of kernel-written obs copies, allocated by _history_tap()
-        self._last_hist = None
-        self._priv = torch.zeros((OUT_RING, n, self.num_privileged_obs), device=dev)
-        self._rew = torch.zeros((OUT_RING, n), device=dev)
-        self._reset = torch.zeros((OUT_RING, n), dtype=torch.bool, device=dev)
-        self._time_out = torch.zeros((OUT_RING, n), dtype=torch.bool, device=dev)
-        self._slot = 0
         # the compact episode log needs the HIP backend's prepared-args path, and rows that the
         # global pos/neg bucket pass (indefinite reward slots) does not rewrite by env index
         self._fast = hasattr(self._sim, "prepare")
@@ -380,59 +309,15 @@ class LeggedRobot:
         self._demand = (True, True)
         # envs the native integrator's divergence guard reset, cumulative (extras["diverged"])
         self._diverged = torch.zeros(1, dtype=torch.int64, device=dev)
-        # host RNG for the global gravity draws: identical on every rank
-        self._host_rng = np.random.default_rng(self.seed)
-        self._n_global = n_global
         self._reset_draws = 0
-        # _init_custom_buffers__ / _randomize_rigid_body_props (:1329-1350, :710-733): per-env draws
-        # keyed by GLOBAL env id (every rank draws the global vector and keeps its slice), so an
-        # N-rank run starts from exactly the state one rank with N x the envs does
-        st = self._sim.state
-        if dr.randomize_friction:
-            lo, hi = dr.friction_range
-            st["friction"].copy_(self._global_uniform(1, lo, hi))
-        else:
-            st["friction"].fill_(1.0)
-        if dr.randomize_restitution:
-            lo, hi = dr.restitution_range
-            st["restitution"].copy_(self._global_uniform(2, lo, hi))
-        if dr.randomize_base_mass:
-            lo, hi = dr.added_mass_range
-            st["payload"].copy_(self._global_uniform(3, lo, hi))
-        st["motor_strength"].fill_(1.0)
-        # gravity (:1574 then :1221): sim gravity drawn, projection vector reset to -z
-        self.common_step_counter = 0
-        self.gravities = np.zeros(3, np.float32)
+        # gravity (:1574 then :1221): sim gravity drawn at creation, projection vector reset to -z
         self._randomize_gravity()
         self._gravity_vec = np.array([0.0, 0.0, -1.0], np.float32)
         self.extras = StepExtras(self)
         self._train_ep, self._eval_ep, self._timeouts = _episode_dicts()
         self._install_extras()
-        self._rng_step = 0
-        # measurement hook (bench.py): hipEvent_t pairs to record around the next steps' kernel
-        self.kernel_events = deque()
 
     # ------------------------------------------------------------------ host state
-    def _global_rng(self, tag):
-        """numpy Philox stream of (seed, tag): the same on every rank, indexed by global env id."""
-        return np.random.Generator(np.random.Philox(key=[self.seed, tag]))
-
-    def _global_uniform(self, tag, lo, hi):
-        """(n, 1) f32 U(lo, hi) for this rank's envs, element i = global env rank * n + i."""
-        u = self._global_rng(tag).random(self._n_global).astype(np.float32)
-        u = u[self.rank * self.num_envs:(self.rank + 1) * self.num_envs, None]
-        return torch.from_numpy(u * np.float32(hi - lo) + np.float32(lo)).to(self.device)
-
-    def _randomize_gravity(self, external_force=None):
-        """_randomize_gravity (:645-660): one global draw shared by every env (and rank)."""
-        if external_force is not None:
-            self.gravities[:] = np.asarray(external_force, np.float32)
-        elif self.cfg.domain_rand.randomize_gravity:
-            lo, hi = self.cfg.domain_rand.gravity_range
-            u = self._host_rng.random(3).astype(np.float32)
-            self.gravities[:] = u * np.float32(hi - lo) + np.float32(lo)
-        self._sim_gravity, self._gravity_vec = CF.gravity_state(self.gravities)
-
     @property
     def gravity_vec(self):
         return torch.as_tensor(self._gravity_vec, device=self.device).repeat(self.num_envs, 1)
@@ -474,56 +359,12 @@ class LeggedRobot:
 
     # ------------------------------------------------------------------ views
     @property
-    def state(self):
-        return self._sim.state
-
-    @property
-    def obs_buf(self):
-        return self._obs[(self._slot - 1) % OUT_RING]
-
-    @property
-    def privileged_obs_buf(self):
-        return self._priv[(self._slot - 1) % OUT_RING]
-
-    @property
-    def rew_buf(self):
-        return self._rew[(self._slot - 1) % OUT_RING]
-
-    @property
-    def reset_buf(self):
-        return self._reset[(self._slot - 1) % OUT_RING]
-
-    @property
-    def time_out_buf(self):
-        return self._time_out[(self._slot - 1) % OUT_RING]
-
-    @property
-    def episode_length_buf(self):
-        return self._sim.state["episode_length"][:, 0]
-
-    @episode_length_buf.setter
-    def episode_length_buf(self, v):
-        self._sim.state["episode_length"][:, 0].copy_(torch.as_tensor(v, device=self.device))
-
-    @property
-    def root_states(self):
-        return self._sim.state["root"]
-
-    @property
     def base_pos(self):
         return self._sim.state["root"][:, 0:3]
 
     @property
     def base_quat(self):
         return self._sim.state["root"][:, 3:7]
-
-    @property
-    def dof_pos(self):
-        return self._sim.state["dof_pos"]
-
-    @property
-    def dof_vel(self):
-        return self._sim.state["dof_vel"]
 
     @property
     def last_actions(self):
@@ -579,9 +420,6 @@ class LeggedRobot:
         s = self._sim.state["episode_sums"]
         return {k: s[:, i] for i, k in enumerate(self.sum_keys)}
 
-    def get_observations(self):
-        return self.obs_buf
-
     def _history_tap(self):
         """Have the step kernel also write each step's obs into a ring of its own: the
         HistoryWrapper's obs_history for a history length of 1 (a fresh copy of obs every
@@ -590,21 +428,10 @@ class LeggedRobot:
             self._obs_hist = torch.zeros_like(self._obs)
         return True
 
-    def get_privileged_observations(self):
-        return self.privileged_obs_buf
-
     # ------------------------------------------------------------------ step
     def step(self, actions):
         """LeggedRobot.step (:64-112): returns obs, privileged_obs, rew, reset, extras."""
-        a = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(actions)
-        if a.device != self.device or a.dtype != torch.float32:
-            a = a.to(self.device, torch.float32)
-        if a.requires_grad:
-            a = a.detach()
-        if not a.is_contiguous():
-            a = a.contiguous()
-        if a.shape != (self.num_envs, self.num_actions):
-            raise ValueError(f"actions must be ({self.num_envs}, {self.num_actions}), got {tuple(a.shape)}")
+        a = self._as_actions(actions)
         s = self._slot
         events = self.kernel_events.popleft() if self.kernel_events else None
         if self._fast:
@@ -632,12 +459,7 @@ class LeggedRobot:
         self._elog.advance()
         self._slot = (s + 1) % OUT_RING
         # post-physics host bookkeeping (:126, :826-830, :171-182)
-        self.common_step_counter += 1
-        c = self.common_step_counter
-        if c % int(self._gravity_interval) == 0:
-            self._randomize_gravity()
-        if int(c - self._gravity_duration) % int(self._gravity_interval) == 0:
-            self._randomize_gravity(np.zeros(3, np.float32))
+        self._tick_gravity_schedule()
         self.update_curriculum()
         return out["obs"], out["priv"], out["rew"], out["reset"], self.extras
 
@@ -665,12 +487,9 @@ class LeggedRobot:
 
     def reset_idx(self, env_ids):
         """reset_idx (:218-296) for explicit ids (the step resets its own envs in the kernel)."""
-        env_ids = torch.as_tensor(env_ids, device=self.device).long().flatten()
-        if env_ids.numel() == 0:
+        env_ids = self._norm_env_ids(env_ids)
+        if env_ids is None:
             return
-        if int(env_ids.min()) < -self.num_envs or int(env_ids.max()) >= self.num_envs:
-            raise IndexError(f"env id out of range for {self.num_envs} envs")  # as the reference's indexing
-        env_ids = torch.remainder(env_ids, self.num_envs)
         self._flush_episode_log()
         st = self._sim.state
         sums = st["episode_sums"][env_ids].cpu().numpy()
@@ -694,31 +513,6 @@ class LeggedRobot:
     def _flush_episode_log(self):
         self._elog.drain()
 
-    # ------------------------------------------------------------------ misc API
-    def start_recording(self):
-        pass
-
-    def pause_recording(self):
-        pass
-
-    def start_recording_eval(self):
-        pass
-
-    def pause_recording_eval(self):
-        pass
-
-    def get_complete_frames(self):
-        return []
-
-    def get_complete_frames_eval(self):
-        return []
-
-    def render(self, mode="rgb_array"):
-        return None
-
-    def close(self):
-        self._sim.close()
-
 
 class TrajectoryTrackingEnv(LeggedRobot):
     """TrajectoryTrackingEnv (trajectory_tracking/__init__.py:11-55)."""
@@ -731,20 +525,9 @@ class TrajectoryTrackingEnv(LeggedRobot):
             cfg.env.num_envs = num_envs
         super().__init__(cfg, None, physics_engine, sim_device, headless, eval_cfg, initial_dynamics_dict, **kw)
         n = self.num_envs
-        ex = self.extras
-        ex.set_lazy("joint_pos", lambda: self.dof_pos.cpu().numpy())
-        ex.set_lazy("joint_vel", lambda: self.dof_vel.cpu().numpy())
-        ex.set_lazy("joint_pos_target", lambda: self.joint_pos_target.cpu().numpy())
-        dict.__setitem__(ex, "joint_vel_target", torch.zeros(12))
-        ex.set_lazy("body_linear_vel", lambda: self.base_lin_vel.cpu().numpy())
-        ex.set_lazy("body_angular_vel", lambda: self.base_ang_vel.cpu().numpy())
-        ex.set_lazy("body_linear_vel_cmd", lambda: self.commands.cpu().numpy())
-        ex.set_lazy("body_angular_vel_cmd", lambda: np.zeros((n, 0), np.float32))
-        ex.set_lazy("contact_states",
-                    lambda: (self.contact_forces[:, list(L.FEET_INDICES), 2] > 1.0).cpu().numpy().copy())
-        ex.set_lazy("foot_positions", lambda: self.foot_positions.cpu().numpy().copy())
-        ex.set_lazy("body_pos", lambda: self.base_pos.cpu().numpy())
-        ex.set_lazy("torques", lambda: self.torques.cpu().numpy())
+        self._install_step_extras(self.extras, body_linear_vel_cmd=lambda: self.commands.cpu().numpy(),
+                                  body_angular_vel_cmd=lambda: np.zeros((n, 0), np.float32),
+                                  body_pos=lambda: self.base_pos.cpu().numpy())
 
     def step(self, actions):
         obs, priv, rew, reset, extras = super().step(actions)

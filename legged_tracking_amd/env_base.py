@@ -1,0 +1,279 @@
+"""What the trajectory env (env.py) and the velocity env (velocity.py) keep on the host in the same way.
+
+EnvBase owns the rank / world-size resolution, dims and seed, the OUT_RING output rings with their *_buf
+views, the state views, the per-env Philox draws keyed by global env id (creation-time domain
+randomisation), the global gravity schedule (_randomize_gravity, _tick_gravity_schedule), the action and
+env-id normalisation, the twelve lazy numpy extras and the reference's recording / render stubs.
+
+Each env keeps what differs: when its step ticks the gravity schedule (after the launch / before it, with
+the pre- and post-tick vectors), the initial gravity draw (trajectory only), its aux column layout,
+set_output_demand, its episode log and its obs-history mechanism.  step() is host-bound, so the helpers
+here are leaf calls: no super().step() chain.
+"""
+from collections import deque
+
+import numpy as np
+import torch
+
+from . import config as CF, layout as L
+
+OUT_RING = 4
+_LAZY = object()
+
+
+def _dist_info():
+    try:
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            return dist.get_rank(), dist.get_world_size()
+    except Exception:
+        pass
+    return 0, 1
+
+
+class StepExtras(dict):
+    """The env's `extras` dict: device-backed entries are materialised on read."""
+
+    def __init__(self, env):
+        super().__init__()
+        self._env = env
+        self._lazy = {}
+
+    def set_lazy(self, key, fn):
+        self._lazy[key] = fn
+        dict.__setitem__(self, key, _LAZY)
+
+    def __getitem__(self, key):
+        if key in ("train/episode", "eval/episode", "timeouts"):
+            self._env._flush_episode_log()
+        v = dict.__getitem__(self, key)
+        return self._lazy[key]() if v is _LAZY else v
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+    def deferred_time_outs(self):
+        """extras["time_outs"] with its pending rebinding left to the consumer: returns
+        (tensor, (flag, pending, dst) device pointers or None).  The PPO record kernel resolves
+        it (rollout.py PPO.process_env_step), saving the sync launch a plain read costs."""
+        return self._env._deferred_time_outs()
+
+    def items(self):
+        return [(k, self[k]) for k in list(self.keys())]
+
+    def values(self):
+        return [self[k] for k in list(self.keys())]
+
+
+class EnvBase:
+    """Host state shared by LeggedRobot and VelocityTrackingEasyEnv.  A subclass calls _init_dims, creates
+    self._sim (a native handle or an injected backend) and self.device, then calls _init_host_state."""
+
+    def _init_dims(self, cfg, derived, sim_device, headless, seed, rank, world_size):
+        if rank is None or world_size is None:
+            r, w = _dist_info()
+            rank = r if rank is None else rank
+            world_size = w if world_size is None else world_size
+        self.rank, self.world_size = rank, world_size
+        self.cfg = cfg
+        self.eval_cfg = None
+        self.sim_device = sim_device
+        self.headless = headless
+        self.num_obs = int(cfg.env.num_observations)
+        self.num_privileged_obs = int(cfg.env.num_privileged_obs)
+        self.num_actions = int(cfg.env.num_actions)
+        self.num_envs = self.num_train_envs = int(cfg.env.num_envs)
+        self.num_eval_envs = 0
+        self._n_global = self.num_envs * world_size
+        self.seed = int(seed)
+        self.dt = derived["dt"]
+        self.max_episode_length = derived["max_episode_length"]
+        self.reward_scales = dict(derived["reward_scales"])
+        self._gravity_interval = int(derived["gravity_rand_interval"])
+        self._gravity_duration = int(derived["gravity_rand_duration"])
+
+    def _init_host_state(self):
+        n, dev, dr = self.num_envs, self.device, self.cfg.domain_rand
+        # output rings: a tensor returned by step() stays valid for OUT_RING - 1 further steps
+        self._obs = torch.zeros((OUT_RING, n, self.num_obs), device=dev)
+        self._priv = torch.zeros((OUT_RING, n, self.num_privileged_obs), device=dev)
+        self._rew = torch.zeros((OUT_RING, n), device=dev)
+        self._reset = torch.zeros((OUT_RING, n), dtype=torch.bool, device=dev)
+        self._time_out = torch.zeros((OUT_RING, n), dtype=torch.bool, device=dev)
+        self._slot = 0
+        self._last_hist = None
+        # _randomize_rigid_body_props at creation: per-env draws keyed by GLOBAL env id (every rank draws the
+        # global vector and keeps its slice), so an N-rank run starts from exactly the state one rank with
+        # N x the envs does
+        st = self._sim.state
+        if dr.randomize_friction:
+            st["friction"].copy_(self._global_uniform(1, *dr.friction_range))
+        else:
+            st["friction"].fill_(1.0)
+        if dr.randomize_restitution:
+            st["restitution"].copy_(self._global_uniform(2, *dr.restitution_range))
+        if dr.randomize_base_mass:
+            st["payload"].copy_(self._global_uniform(3, *dr.added_mass_range))
+        st["motor_strength"].fill_(1.0)
+        # gravity: Cfg.sim.gravity and the projection vector -z until the first draw; the draws come from
+        # one host RNG that is identical on every rank
+        self._host_rng = np.random.default_rng(self.seed)
+        self.common_step_counter = 0
+        self.gravities = np.zeros(3, np.float32)
+        self._sim_gravity = np.asarray(self.cfg.sim.gravity, np.float32)
+        self._gravity_vec = np.array([0.0, 0.0, -1.0], np.float32)
+        self._grav_version = 0  # bumped by every _randomize_gravity
+        self._rng_step = 0
+        # measurement hook (bench.py): hipEvent_t pairs to record around the next steps' kernel
+        self.kernel_events = deque()
+
+    # ------------------------------------------------------------------ host draws
+    def _global_rng(self, tag):
+        """numpy Philox stream of (seed, tag): the same on every rank, indexed by global env id."""
+        return np.random.Generator(np.random.Philox(key=[self.seed, tag]))
+
+    def _global_uniform(self, tag, lo, hi):
+        """(n, 1) f32 U(lo, hi) for this rank's envs, element i = global env rank * n + i."""
+        u = self._global_rng(tag).random(self._n_global).astype(np.float32)
+        u = u[self.rank * self.num_envs:(self.rank + 1) * self.num_envs, None]
+        return torch.from_numpy(u * np.float32(hi - lo) + np.float32(lo)).to(self.device)
+
+    def _randomize_gravity(self, external_force=None):
+        """_randomize_gravity: one global draw shared by every env (and rank).  It replaces the
+        _sim_gravity / _gravity_vec arrays, so references taken before it keep the old values."""
+        if external_force is not None:
+            self.gravities[:] = np.asarray(external_force, np.float32)
+        elif self.cfg.domain_rand.randomize_gravity:
+            lo, hi = self.cfg.domain_rand.gravity_range
+            u = self._host_rng.random(3).astype(np.float32)
+            self.gravities[:] = u * np.float32(hi - lo) + np.float32(lo)
+        self._sim_gravity, self._gravity_vec = CF.gravity_state(self.gravities)
+        self._grav_version += 1
+
+    def _tick_gravity_schedule(self):
+        """common_step_counter and the global schedule: a draw every gravity_rand_interval steps, zeroed
+        gravity_rand_duration steps later."""
+        self.common_step_counter += 1
+        c, gi = self.common_step_counter, self._gravity_interval
+        if c % gi == 0:
+            self._randomize_gravity()
+        if (c - self._gravity_duration) % gi == 0:
+            self._randomize_gravity(np.zeros(3, np.float32))
+
+    # ------------------------------------------------------------------ argument normalisation
+    def _as_actions(self, actions):
+        """The step's actions as a contiguous f32 (num_envs, num_actions) tensor on the env's device."""
+        a = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(actions)
+        if a.device != self.device or a.dtype != torch.float32:
+            a = a.to(self.device, torch.float32)
+        if a.requires_grad:
+            a = a.detach()
+        if not a.is_contiguous():
+            a = a.contiguous()
+        if a.shape != (self.num_envs, self.num_actions):
+            raise ValueError(f"actions must be ({self.num_envs}, {self.num_actions}), got {tuple(a.shape)}")
+        return a
+
+    def _norm_env_ids(self, env_ids):
+        """reset_idx's ids as a flat int64 tensor in [0, num_envs) (negative ids wrap, out-of-range ids raise
+        as the reference's indexing does); None for an empty list."""
+        env_ids = torch.as_tensor(env_ids, device=self.device).long().flatten()
+        if env_ids.numel() == 0:
+            return None
+        if int(env_ids.min()) < -self.num_envs or int(env_ids.max()) >= self.num_envs:
+            raise IndexError(f"env id out of range for {self.num_envs} envs")
+        return torch.remainder(env_ids, self.num_envs)
+
+    # ------------------------------------------------------------------ views
+    @property
+    def state(self):
+        return self._sim.state
+
+    @property
+    def obs_buf(self):
+        return self._obs[(self._slot - 1) % OUT_RING]
+
+    @property
+    def privileged_obs_buf(self):
+        return self._priv[(self._slot - 1) % OUT_RING]
+
+    @property
+    def rew_buf(self):
+        return self._rew[(self._slot - 1) % OUT_RING]
+
+    @property
+    def reset_buf(self):
+        return self._reset[(self._slot - 1) % OUT_RING]
+
+    @property
+    def time_out_buf(self):
+        return self._time_out[(self._slot - 1) % OUT_RING]
+
+    @property
+    def episode_length_buf(self):
+        return self._sim.state["episode_length"][:, 0]
+
+    @episode_length_buf.setter
+    def episode_length_buf(self, v):
+        self._sim.state["episode_length"][:, 0].copy_(torch.as_tensor(v, device=self.device))
+
+    @property
+    def root_states(self):
+        return self._sim.state["root"]
+
+    @property
+    def dof_pos(self):
+        return self._sim.state["dof_pos"]
+
+    @property
+    def dof_vel(self):
+        return self._sim.state["dof_vel"]
+
+    def get_observations(self):
+        return self.obs_buf
+
+    def get_privileged_observations(self):
+        return self.privileged_obs_buf
+
+    # ------------------------------------------------------------------ extras
+    def _install_step_extras(self, ex, body_linear_vel_cmd, body_angular_vel_cmd, body_pos):
+        """The numpy extras the reference's step builds every time, computed on read (no device->host copy
+        per step); the three arguments are the entries that differ between the tasks."""
+        ex.set_lazy("joint_pos", lambda: self.dof_pos.cpu().numpy())
+        ex.set_lazy("joint_vel", lambda: self.dof_vel.cpu().numpy())
+        ex.set_lazy("joint_pos_target", lambda: self.joint_pos_target.cpu().numpy())
+        dict.__setitem__(ex, "joint_vel_target", torch.zeros(12))
+        ex.set_lazy("body_linear_vel", lambda: self.base_lin_vel.cpu().numpy())
+        ex.set_lazy("body_angular_vel", lambda: self.base_ang_vel.cpu().numpy())
+        ex.set_lazy("body_linear_vel_cmd", body_linear_vel_cmd)
+        ex.set_lazy("body_angular_vel_cmd", body_angular_vel_cmd)
+        ex.set_lazy("contact_states",
+                    lambda: (self.contact_forces[:, list(L.FEET_INDICES), 2] > 1.0).cpu().numpy().copy())
+        ex.set_lazy("foot_positions", lambda: self.foot_positions.cpu().numpy().copy())
+        ex.set_lazy("body_pos", body_pos)
+        ex.set_lazy("torques", lambda: self.torques.cpu().numpy())
+
+    # ------------------------------------------------------------------ misc API
+    def start_recording(self):
+        pass
+
+    def pause_recording(self):
+        pass
+
+    def start_recording_eval(self):
+        pass
+
+    def pause_recording_eval(self):
+        pass
+
+    def get_complete_frames(self):
+        return []
+
+    def get_complete_frames_eval(self):
+        return []
+
+    def render(self, mode="rgb_array"):
+        return None
+
+    def close(self):
+        self._sim.close()

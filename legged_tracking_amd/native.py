@@ -5,12 +5,13 @@ in the HIP library legged_tracking_amd/_build/libgo1_mi355x.so.  If that library
 is missing or the GPU is absent this module raises -- there is no CPU fallback.
 """
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import torch
 
-from . import abi, layout as L
+from . import abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GO1_LIB_OVERRIDE") or os.path.join(HERE, "_build", "libgo1_mi355x.so")
@@ -21,42 +22,87 @@ class NativeError(RuntimeError):
     pass
 
 
-def lib():
-    """Load the HIP library (fails loudly; build with __graft_entry__.build())."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise NativeError(f"HIP extension missing: {LIB_PATH} (run python -c 'import __graft_entry__ as g; g.build()')")
-    l = C.CDLL(LIB_PATH)
-    l.go1_abi_version.restype = C.c_int
-    l.go1_last_error.restype = C.c_char_p
-    l.go1_create.argtypes = [C.POINTER(abi.Go1Config), C.POINTER(C.c_void_p)]
-    l.go1_bind.argtypes = [C.c_void_p, C.POINTER(abi.Go1State), C.POINTER(abi.Go1Plane)]
-    l.go1_set_terrain.argtypes = [C.c_void_p, C.POINTER(abi.Go1Terrain)]
-    l.go1_step.argtypes = [C.c_void_p, C.POINTER(abi.Go1StepArgs), C.c_void_p]
-    l.go1_reset_envs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
-    l.go1_reset_idx.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
-    l.go1_sync_time_outs.argtypes = [C.c_void_p, C.c_void_p]
-    l.go1_time_outs_pending.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    l.go1_actuator_net.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    l.go1_destroy.argtypes = [C.c_void_p]
-    l.go1_specialize.argtypes = [C.c_void_p, C.c_int]
-    l.go1_is_specialized.argtypes = [C.c_void_p]
-    l.go1_tunnel_tiles.argtypes = [C.POINTER(abi.Go1TunnelParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    if l.go1_abi_version() != abi.GO1_ABI_VERSION:
-        raise NativeError("ABI version mismatch")
-    _lib = l
+def load_library(path, version_fn, version, error_fn, argtypes):
+    """dlopen a HIP library of this package, set its prototypes and check its ABI version (fails loudly;
+    build with __graft_entry__.build()).  `argtypes` is {function: [ctypes types]}; the loaded library
+    carries `last_error` for check()."""
+    if not os.path.exists(path):
+        raise NativeError(f"HIP extension missing: {path} (run python -c 'import __graft_entry__ as g; g.build()')")
+    l = C.CDLL(path)
+    getattr(l, version_fn).restype = C.c_int
+    l.last_error = getattr(l, error_fn)
+    l.last_error.restype = C.c_char_p
+    for name, types in argtypes.items():
+        getattr(l, name).argtypes = types
+    if getattr(l, version_fn)() != version:
+        raise NativeError(f"ABI version mismatch: {path} is not version {version} ({version_fn})")
     return l
 
 
-def _check(rc):
+def check(l, rc):
     if rc != 0:
-        raise NativeError(lib().go1_last_error().decode())
+        raise NativeError(l.last_error().decode())
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+_ARGTYPES = {
+    "go1_create": [C.POINTER(abi.Go1Config), C.POINTER(C.c_void_p)],
+    "go1_bind": [C.c_void_p, C.POINTER(abi.Go1State), C.POINTER(abi.Go1Plane)],
+    "go1_set_terrain": [C.c_void_p, C.POINTER(abi.Go1Terrain)],
+    "go1_step": [C.c_void_p, C.POINTER(abi.Go1StepArgs), C.c_void_p],
+    "go1_reset_envs": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p],
+    "go1_reset_idx": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p],
+    "go1_sync_time_outs": [C.c_void_p, C.c_void_p],
+    "go1_time_outs_pending": [C.c_void_p, C.POINTER(C.c_int64)],
+    "go1_actuator_net": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
+    "go1_destroy": [C.c_void_p],
+    "go1_specialize": [C.c_void_p, C.c_int],
+    "go1_is_specialized": [C.c_void_p],
+    "go1_tunnel_tiles": [C.POINTER(abi.Go1TunnelParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+
+
+def lib():
+    """The HIP step library, loaded once."""
+    global _lib
+    if _lib is None:
+        _lib = load_library(LIB_PATH, "go1_abi_version", abi.GO1_ABI_VERSION, "go1_last_error", _ARGTYPES)
+    return _lib
+
+
+class NativeHandle:
+    """Base of the handle owners (Go1Native, velocity.VelNative): the device, the caller's current raw stream
+    on it, reset_idx's id conversion and close / __del__ through the library's destroy function."""
+    WHAT = "step"
+
+    def _open(self, device, l, destroy):
+        if not torch.cuda.is_available():
+            raise NativeError(f"no GPU visible: the MI355X {self.WHAT} has no CPU fallback")
+        self.device = torch.device(device)
+        self.h = C.c_void_p()
+        self._lib, self._destroy = l, destroy
+        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        # hipStream_t (as an int) of torch's current stream on the handle's device; a partial of the C
+        # function, because the per-step path calls it
+        self._stream = functools.partial(torch._C._cuda_getCurrentRawStream, self._dev_index)
+
+    def _check(self, rc):
+        check(self._lib, rc)
+
+    def _ids(self, env_ids):
+        """Local env ids (any integer tensor or list) as a contiguous int32 tensor on the device; the caller
+        keeps it alive until the stream passes it."""
+        return torch.as_tensor(env_ids, device=self.device).to(torch.int32).flatten().contiguous()
+
+    def close(self):
+        if self.h:
+            self._destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def tunnel_tiles(cfg_terrain, layout, seed, device):
@@ -83,7 +129,8 @@ def tunnel_tiles(cfg_terrain, layout, seed, device):
     rec = torch.empty((rows * cols, abi.GO1_TUNNEL_REC), dtype=torch.float64, device=device)
     tiles = torch.empty((rows, cols, 2, layout.tile_x, layout.tile_y), dtype=torch.float32, device=device)
     with torch.cuda.device(device):
-        _check(lib().go1_tunnel_tiles(C.byref(p), ext.data_ptr(), rec.data_ptr(), tiles.data_ptr(), _stream()))
+        check(lib(), lib().go1_tunnel_tiles(C.byref(p), ext.data_ptr(), rec.data_ptr(), tiles.data_ptr(),
+                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     torch.cuda.current_stream(device).synchronize()  # ext / rec are freed on return
     return tiles
 
@@ -112,18 +159,18 @@ class StateTensors:
         return {k: v.cpu().numpy() for k, v in self.t.items()}
 
 
-class Go1Native:
+OUT_KEYS = ("obs", "priv", "rew", "reset", "time_out")
+
+
+class Go1Native(NativeHandle):
     """Owns one go1_handle and the device buffers the C ABI writes."""
 
     def __init__(self, cfg: abi.Go1Config, device="cuda:0"):
-        if not torch.cuda.is_available():
-            raise NativeError("no GPU visible: the MI355X step has no CPU fallback")
-        self.device = torch.device(device)
+        self._open(device, lib(), lib().go1_destroy)
         self.cfg = cfg
         self.n = n = cfg.n_envs
-        self.h = C.c_void_p()
         with torch.cuda.device(self.device):
-            _check(lib().go1_create(C.byref(cfg), C.byref(self.h)))
+            self._check(self._lib.go1_create(C.byref(cfg), C.byref(self.h)))
             self.state = StateTensors(n, self.device, cfg)
             self.bind(self.state)
             dev = self.device
@@ -136,16 +183,14 @@ class Go1Native:
             self.contact_forces = torch.zeros((n, 17, 3), device=dev)
         self._terrain_keep = None
         self._args = None
-        self._consts = None
-        self._lib_step = lib().go1_step
-        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self._lib_step = self._lib.go1_step
 
     def bind(self, state):
         """go1_bind the planes of `state` (StateTensors or {name: tensor}); the library checks their
         shapes, dtypes and strides and raises NativeError for anything but dense (n_envs, width)."""
         t = state.t if hasattr(state, "t") else state
         s = abi.Go1State(**{k: t[k].data_ptr() for k, _ in abi.Go1State._fields_})
-        _check(lib().go1_bind(self.h, C.byref(s), abi.plane_descs(t)))
+        self._check(self._lib.go1_bind(self.h, C.byref(s), abi.plane_descs(abi.Go1State._fields_, t)))
 
     def set_terrain(self, tiles, env_tile, env_terrain_origin, env_origins):
         d = self.device
@@ -160,7 +205,69 @@ class Go1Native:
         self._terrain_keep = t
         s = abi.Go1Terrain(tiles=t[0].data_ptr(), env_tile=t[1].data_ptr(), env_terrain_origin=t[2].data_ptr(),
                            env_origins=t[3].data_ptr(), n_tiles=int(t[0].shape[0]))
-        _check(lib().go1_set_terrain(self.h, C.byref(s)))
+        self._check(self._lib.go1_set_terrain(self.h, C.byref(s)))
+
+    # ------------------------------------------------------------------ argument checks shared by the step forms
+    def _new_args(self):
+        a = abi.Go1StepArgs()
+        a.extras_time_outs = self.extras_time_outs.data_ptr()
+        a._consts = None  # key of the gravity / reward-scale values the block holds
+        return a
+
+    def _check_actions(self, a, actions):
+        if actions.dtype != torch.float32 or actions.shape != (self.n, 12) or not actions.is_contiguous() or \
+                actions.device != self.device:
+            raise NativeError("actions must be a contiguous (n_envs, 12) float32 tensor on the env's device")
+        a.actions = actions.data_ptr()
+
+    def _check_out(self, a, out):
+        """Output pointers: the buffers of `out` (checked), the handle's own for keys it leaves out."""
+        for k in OUT_KEYS:
+            ref = getattr(self, k)
+            v = out.get(k) if out else None
+            if v is None:
+                v = ref
+            elif v.device != self.device or not v.is_contiguous() or v.shape != ref.shape or v.dtype != ref.dtype:
+                raise NativeError(f"output buffer {k!r} does not match the expected shape / dtype / device")
+            setattr(a, k, v.data_ptr())
+
+    def _write_consts(self, a, gvec, sgrav, scales):
+        a.gravity_vec[:] = [float(x) for x in gvec]
+        a.sim_gravity[:] = [float(x) for x in sgrav]
+        rs = np.zeros(abi.GO1_MAX_TERMS, np.float32)
+        rs[:len(scales)] = np.asarray(scales, np.float32)
+        a.reward_scales[:] = [float(x) for x in rs]
+
+    def _check_optional(self, a, contact_forces, aux, obs_history, diverged_count, episode_log, log_count=None):
+        """Validate the optional buffers and write their pointers (None -> NULL: the kernel skips that store).
+        `episode_log` with `log_count` selects the compact log (go1_step_args.episode_log_count)."""
+        a.contact_forces = self.contact_forces.data_ptr() if contact_forces else None
+        if aux is not None and (not aux.is_contiguous() or aux.shape != (self.n, abi.GO1_AUX) or
+                                aux.device != self.device):
+            raise NativeError("aux must be a contiguous (n_envs, GO1_AUX) float32 tensor on the env's device")
+        a.aux = aux.data_ptr() if aux is not None else None
+        if obs_history is not None and (not obs_history.is_contiguous() or
+                                        obs_history.shape != (self.n, self.cfg.num_obs)):
+            raise NativeError("obs_history must be a contiguous (n_envs, num_obs) tensor")
+        a.obs_history = obs_history.data_ptr() if obs_history is not None else None
+        if diverged_count is not None and (diverged_count.dtype != torch.int64 or diverged_count.numel() != 1 or
+                                           diverged_count.device != self.device):
+            raise NativeError("diverged_count must be one int64 on the env's device")
+        a.diverged_count = diverged_count.data_ptr() if diverged_count is not None else None
+        a.episode_log_count, a.episode_log_cap = None, 0
+        if episode_log is not None:
+            w = abi.episode_log_width(self.cfg.n_terms)
+            if log_count is None:
+                if episode_log.shape != (self.n, w) or not episode_log.is_contiguous():
+                    raise NativeError("episode_log must be a contiguous (n_envs, n_terms + 6) tensor")
+            else:
+                if episode_log.dim() != 2 or episode_log.shape[1] != w + 2 or not episode_log.is_contiguous() or \
+                        log_count.dtype != torch.int32 or log_count.device != self.device:
+                    raise NativeError("a compact episode log is a contiguous (cap, n_terms + 8) tensor + an int32 "
+                                      "count")
+                a.episode_log_count = log_count.data_ptr()
+                a.episode_log_cap = int(episode_log.shape[0])
+        a.episode_log = episode_log.data_ptr() if episode_log is not None else None
 
     def step(self, actions, gravity_vec, sim_gravity, reward_scales, rng_seed=0, rng_step=0, uniforms=None,
              inj=None, debug=None, events=None, episode_log=None, aux=None, out=None, obs_history=None,
@@ -174,60 +281,29 @@ class Go1Native:
         few hundred microseconds); only the fields that change are rewritten."""
         a = self._args
         if a is None:
-            a = self._args = abi.Go1StepArgs()
-            a.extras_time_outs = self.extras_time_outs.data_ptr()
-        a.contact_forces = self.contact_forces.data_ptr() if contact_forces else None
-        if actions.dtype != torch.float32 or actions.shape != (self.n, 12) or not actions.is_contiguous() or \
-                actions.device != self.device:
-            raise NativeError("actions must be a contiguous (n_envs, 12) float32 tensor on the env's device")
-        a.actions = actions.data_ptr()
+            a = self._args = self._new_args()
+        self._check_actions(a, actions)
         key = (tuple(gravity_vec), tuple(sim_gravity), tuple(reward_scales))
-        if key != self._consts:
-            self._consts = key
-            a.gravity_vec[:] = [float(x) for x in gravity_vec]
-            a.sim_gravity[:] = [float(x) for x in sim_gravity]
-            rs = np.zeros(abi.GO1_MAX_TERMS, np.float32)
-            rs[:len(reward_scales)] = np.asarray(reward_scales, np.float32)
-            a.reward_scales[:] = [float(x) for x in rs]
+        if key != a._consts:
+            a._consts = key
+            self._write_consts(a, gravity_vec, sim_gravity, reward_scales)
         a.rng_seed, a.rng_step = int(rng_seed), int(rng_step)
-        a.uniforms = None
-        if uniforms is not None:
-            assert uniforms.is_contiguous() and uniforms.shape == (self.n, self.cfg.u_per_env)
-            a.uniforms = uniforms.data_ptr()
+        if uniforms is not None and (not uniforms.is_contiguous() or uniforms.shape != (self.n, self.cfg.u_per_env)):
+            raise NativeError("uniforms must be a contiguous (n_envs, u_per_env) tensor")
+        a.uniforms = uniforms.data_ptr() if uniforms is not None else None
         if inj is not None:
             a.inj_dof, a.inj_root, a.inj_contact = (inj[k].data_ptr() for k in ("dof", "root", "contact"))
         else:
             a.inj_dof = a.inj_root = a.inj_contact = None
-        if out:
-            for k in ("obs", "priv", "rew", "reset", "time_out"):
-                v = out.get(k)
-                if v is None:
-                    v = getattr(self, k)
-                elif v.device != self.device or not v.is_contiguous() or v.shape != getattr(self, k).shape or \
-                        v.dtype != getattr(self, k).dtype:
-                    raise NativeError(f"output buffer {k!r} does not match the expected shape / dtype / device")
-                setattr(a, k, v.data_ptr())
-        else:
-            a.obs, a.priv, a.rew = self.obs.data_ptr(), self.priv.data_ptr(), self.rew.data_ptr()
-            a.reset, a.time_out = self.reset.data_ptr(), self.time_out.data_ptr()
+        self._check_out(a, out)
         for k, fld in (("torques", "dbg_torques"), ("heights", "dbg_heights"), ("terms", "dbg_terms"),
                        ("commands", "dbg_commands"), ("reached", "dbg_reached")):
             setattr(a, fld, debug[k].data_ptr() if debug and k in debug else None)
-        if episode_log is not None:
-            assert episode_log.is_contiguous() and episode_log.shape == (self.n, abi.episode_log_width(self.cfg.n_terms))
-        a.episode_log = episode_log.data_ptr() if episode_log is not None else None
-        if aux is not None:
-            assert aux.is_contiguous() and aux.shape == (self.n, abi.GO1_AUX)
-        a.aux = aux.data_ptr() if aux is not None else None
+        self._check_optional(a, contact_forces, aux, obs_history, diverged_count, episode_log)
         a.ev_begin, a.ev_end = events if events is not None else (None, None)  # hipEvent_t pair as ints
-        if obs_history is not None:
-            assert obs_history.is_contiguous() and obs_history.shape == (self.n, self.cfg.num_obs)
-        a.obs_history = obs_history.data_ptr() if obs_history is not None else None
-        if diverged_count is not None:
-            assert diverged_count.dtype == torch.int64 and diverged_count.numel() == 1 and \
-                diverged_count.device == self.device
-        a.diverged_count = diverged_count.data_ptr() if diverged_count is not None else None
-        _check(self._lib_step(self.h, C.byref(a), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        rc = self._lib_step(self.h, C.byref(a), self._stream())
+        if rc:
+            self._check(rc)
 
     # ------------------------------------------------------------------ per-step fast path
     def prepare(self, out, aux=None, obs_history=None, diverged_count=None, episode_log=None, log_count=None,
@@ -237,115 +313,67 @@ class Go1Native:
         ctypes call (the loop is otherwise host-bound at ~60 us per step).  `episode_log` with
         `log_count` selects the compact log (go1_step_args.episode_log_count); contact_forces=False
         leaves the contact-force store out."""
-        a = abi.Go1StepArgs()
-        a.contact_forces = self.contact_forces.data_ptr() if contact_forces else None
-        a.extras_time_outs = self.extras_time_outs.data_ptr()
-        for k in ("obs", "priv", "rew", "reset", "time_out"):
-            v, ref = out[k], getattr(self, k)
-            if v.device != self.device or not v.is_contiguous() or v.shape != ref.shape or v.dtype != ref.dtype:
-                raise NativeError(f"output buffer {k!r} does not match the expected shape / dtype / device")
-            setattr(a, k, v.data_ptr())
-        if aux is not None:
-            if not aux.is_contiguous() or aux.shape != (self.n, abi.GO1_AUX) or aux.device != self.device:
-                raise NativeError("aux must be a contiguous (n_envs, GO1_AUX) float32 tensor on the env's device")
-            a.aux = aux.data_ptr()
-        if obs_history is not None:
-            if not obs_history.is_contiguous() or obs_history.shape != (self.n, self.cfg.num_obs):
-                raise NativeError("obs_history must be a contiguous (n_envs, num_obs) tensor")
-            a.obs_history = obs_history.data_ptr()
-        if diverged_count is not None:
-            if diverged_count.dtype != torch.int64 or diverged_count.numel() != 1 or \
-                    diverged_count.device != self.device:
-                raise NativeError("diverged_count must be one int64 on the env's device")
-            a.diverged_count = diverged_count.data_ptr()
-        if episode_log is not None:
-            w = abi.episode_log_width(self.cfg.n_terms)
-            if log_count is None:
-                if episode_log.shape != (self.n, w) or not episode_log.is_contiguous():
-                    raise NativeError("episode_log must be a contiguous (n_envs, n_terms + 6) tensor")
-            else:
-                if episode_log.dim() != 2 or episode_log.shape[1] != w + 2 or not episode_log.is_contiguous() or \
-                        log_count.dtype != torch.int32 or log_count.device != self.device:
-                    raise NativeError("a compact episode log is a contiguous (cap, n_terms + 8) tensor + an int32 count")
-                a.episode_log_count = log_count.data_ptr()
-                a.episode_log_cap = int(episode_log.shape[0])
-            a.episode_log = episode_log.data_ptr()
-        a._consts = None
+        a = self._new_args()
+        self._check_out(a, out)
+        self._check_optional(a, contact_forces, aux, obs_history, diverged_count, episode_log, log_count)
         return a
 
     def step_prepared(self, a, actions, gravity_vec, sim_gravity, reward_scales, consts_key, rng_seed, rng_step,
                       events=None, log_tag=0):
         """go1_step with a prepare()d argument block.  `consts_key` identifies (gravity_vec,
         sim_gravity, reward_scales): they are re-copied into the block only when it changes."""
-        if actions.dtype != torch.float32 or actions.shape != (self.n, 12) or not actions.is_contiguous() or \
-                actions.device != self.device:
-            raise NativeError("actions must be a contiguous (n_envs, 12) float32 tensor on the env's device")
-        a.actions = actions.data_ptr()
+        self._check_actions(a, actions)
         if a._consts != consts_key:
             a._consts = consts_key
-            a.gravity_vec[:] = [float(x) for x in gravity_vec]
-            a.sim_gravity[:] = [float(x) for x in sim_gravity]
-            rs = np.zeros(abi.GO1_MAX_TERMS, np.float32)
-            rs[:len(reward_scales)] = np.asarray(reward_scales, np.float32)
-            a.reward_scales[:] = [float(x) for x in rs]
+            self._write_consts(a, gravity_vec, sim_gravity, reward_scales)
         a.rng_seed, a.rng_step, a.episode_log_tag = rng_seed, rng_step, log_tag
         a.ev_begin, a.ev_end = events if events is not None else (None, None)
-        rc = self._lib_step(self.h, C.byref(a), torch._C._cuda_getCurrentRawStream(self._dev_index))
+        rc = self._lib_step(self.h, C.byref(a), self._stream())
         if rc:
-            _check(rc)
+            self._check(rc)
 
     def specialize(self, enable):
         """Force the generic step kernel (False) or the README-config specialisation (True; raises
         if this config differs from it).  go1_create picks the specialisation when it applies."""
-        _check(lib().go1_specialize(self.h, int(bool(enable))))
+        self._check(self._lib.go1_specialize(self.h, int(bool(enable))))
 
     @property
     def specialized(self):
-        return bool(lib().go1_is_specialized(self.h))
+        return bool(self._lib.go1_is_specialized(self.h))
 
     def sync_time_outs(self):
         """Make extras_time_outs current for the last step (the rebinding of step k is
         otherwise applied by the kernel of step k+1)."""
-        _check(lib().go1_sync_time_outs(self.h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        self._check(self._lib.go1_sync_time_outs(self.h, self._stream()))
         return self.extras_time_outs
 
     def time_outs_pending(self):
         """(flag, pending, extras) device pointers of the last step's deferred extras["time_outs"]
         rebinding (None before the first step); see go1_time_outs_pending."""
         out = (C.c_int64 * 3)()
-        _check(lib().go1_time_outs_pending(self.h, out))
+        self._check(self._lib.go1_time_outs_pending(self.h, out))
         return tuple(int(x) for x in out) if out[0] else None
 
     def reset_idx(self, env_ids, uniforms=None, rng_seed=0, rng_step=0):
         """go1_reset_idx for local env ids (any integer tensor; converted to int32 on the device)."""
-        ids = torch.as_tensor(env_ids, device=self.device).to(torch.int32).flatten().contiguous()
-        _check(lib().go1_reset_idx(self.h, ids.data_ptr(), int(ids.numel()),
-                                   None if uniforms is None else uniforms.data_ptr(), int(rng_seed), int(rng_step),
-                                   _stream()))
-        return ids  # keep alive until the stream passes it
+        ids = self._ids(env_ids)
+        self._check(self._lib.go1_reset_idx(self.h, ids.data_ptr(), int(ids.numel()),
+                                            None if uniforms is None else uniforms.data_ptr(), int(rng_seed),
+                                            int(rng_step), self._stream()))
+        return ids
 
     def reset_envs(self, mask, uniforms=None, rng_seed=0, rng_step=0):
         m = mask.to(torch.uint8).contiguous()
-        _check(lib().go1_reset_envs(self.h, m.data_ptr(), None if uniforms is None else uniforms.data_ptr(),
-                                    int(rng_seed), int(rng_step), _stream()))
+        self._check(self._lib.go1_reset_envs(self.h, m.data_ptr(),
+                                             None if uniforms is None else uniforms.data_ptr(), int(rng_seed),
+                                             int(rng_step), self._stream()))
         return m  # keep alive until the stream passes it
 
     def actuator(self, x):
         x = x.contiguous()
         out = torch.empty(x.shape[0], device=x.device)
-        _check(lib().go1_actuator_net(self.h, x.data_ptr(), out.data_ptr(), x.shape[0], _stream()))
+        self._check(self._lib.go1_actuator_net(self.h, x.data_ptr(), out.data_ptr(), x.shape[0], self._stream()))
         return out
-
-    def close(self):
-        if self.h:
-            lib().go1_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def debug_buffers(n, decimation, device):

@@ -6,6 +6,7 @@ compiled library.
 import ctypes as C
 
 from . import vel_layout as VL
+from .abi import GO1_DTYPE_F64  # noqa: F401  (the f64 plane tag of go1_plane, shared with abi.py)
 
 GO1_VEL_ABI_VERSION = 2
 GO1_VEL_NUM_COMMANDS = VL.NUM_COMMANDS
@@ -18,7 +19,6 @@ GO1_VEL_MAX_BINS = 1024
 GO1_VEL_AUX = 42
 GO1_VEL_U_PER_ENV = VL.VU_PER_ENV
 GO1_VEL_D_PER_ENV = VL.VD_PER_ENV
-GO1_DTYPE_F64 = 2
 
 # enum go1_vel_term
 VTERM_IDS = {name: i for i, name in enumerate((

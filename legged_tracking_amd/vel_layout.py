@@ -29,27 +29,4 @@ VD_CHOICE_A = 0            # rng.choice uniform (periodic resample), then 15 rng
 VD_CHOICE_B = 16           # the same for the resample in reset_idx
 VD_PER_ENV = 32
 
-# ---- velocity state planes (beside the physics planes of go1_state), SoA (n_envs, width)
-def vel_state_spec(n_terms):
-    return (
-        ("commands", NUM_COMMANDS, "f32"),
-        ("gait_indices", 1, "f32"),
-        ("last_last_actions", 12, "f32"),
-        ("last_joint_pos_target", 12, "f32"),
-        ("last_last_joint_pos_target", 12, "f32"),
-        ("command_sums", n_terms + N_COMMAND_SUM_EXTRA, "f32"),
-        ("episode_sums", n_terms + 1, "f32"),     # reward_scales order, then "total" (:1433-1437)
-        ("command_bins", 1, "i32"),
-        ("command_categories", 1, "i32"),
-    )
-
-
-# CoRLRewards functions the velocity step implements, by name (go1_gym/envs/rewards/corl_rewards.py);
-# a nonzero-scaled term outside this table raises (the reference prints a warning and skips a name
-# the container lacks, :1426-1427; every train_velocity_tracking.py term exists)
-VTERMS = ("tracking_lin_vel", "tracking_ang_vel", "lin_vel_z", "ang_vel_xy", "orientation", "torques",
-          "dof_acc", "action_rate", "collision", "dof_pos_limits", "jump", "tracking_contacts_shaped_force",
-          "tracking_contacts_shaped_vel", "dof_pos", "dof_vel", "action_smoothness_1", "action_smoothness_2",
-          "feet_slip", "feet_contact_vel", "feet_contact_forces", "feet_clearance_cmd_linear", "feet_impact_vel",
-          "orientation_control", "raibert_heuristic")
-VTERM_IDS = {name: i for i, name in enumerate(VTERMS)}
+# The state planes and the reward-term ids are tabulated once, in vel_abi.VEL_STATE_SPEC / vel_abi.VTERM_IDS.

@@ -18,59 +18,41 @@ of torch's global generator and the curricula's RandomState, output tensors rota
 buffers, and the interval resample of a step runs ahead in the previous step's curriculum launch.
 """
 import ctypes as C
-import math
 import os
-from collections import deque
 
 import numpy as np
 import torch
 
 from . import abi, config as CF, layout as L, vel_abi as VA, vel_layout as VL, velocity_config as V
+from .env_base import OUT_RING, EnvBase, StepExtras  # noqa: F401  (OUT_RING: importable from here)
+from .native import NativeError, NativeHandle, load_library  # noqa: F401  (NativeError: the one class)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GO1_VEL_LIB_OVERRIDE") or os.path.join(HERE, "_build", "libgo1_velocity.so")
-OUT_RING = 4
 # obs_history windows per wide buffer: the history lives in rows of width W + 70 x HIST_WINDOW, and each step
 # returns the next W-wide window of the row (go1_vel_step's sliding-window form, no shift); the rows are
 # rewound -- the last W - 70 columns shifted into the other buffer -- once every HIST_WINDOW steps
 HIST_WINDOW = 32
 _lib = None
-
-
-class NativeError(RuntimeError):
-    pass
+_ARGTYPES = {
+    "go1_vel_abi_sizes": [C.POINTER(C.c_int64)],
+    "go1_vel_create": [C.POINTER(abi.Go1Config), C.POINTER(VA.Go1VelConfig), C.c_void_p, C.POINTER(C.c_void_p)],
+    "go1_vel_bind": [C.c_void_p, C.POINTER(VA.Go1VelState), C.POINTER(abi.Go1Plane)],
+    "go1_vel_set_origins": [C.c_void_p, C.c_void_p],
+    "go1_vel_step": [C.c_void_p, C.POINTER(VA.Go1VelStepArgs), C.c_void_p],
+    "go1_vel_reset_idx": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                          C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
+    "go1_vel_resample": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p],
+    "go1_vel_destroy": [C.c_void_p],
+}
 
 
 def lib():
-    """Load the HIP velocity library (fails loudly; build with __graft_entry__.build())."""
+    """The HIP velocity library, loaded once."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise NativeError(f"HIP extension missing: {LIB_PATH} (run python -c 'import __graft_entry__ as g; g.build()')")
-    l = C.CDLL(LIB_PATH)
-    l.go1_vel_abi_version.restype = C.c_int
-    l.go1_vel_last_error.restype = C.c_char_p
-    l.go1_vel_abi_sizes.argtypes = [C.POINTER(C.c_int64)]
-    l.go1_vel_create.argtypes = [C.POINTER(abi.Go1Config), C.POINTER(VA.Go1VelConfig), C.c_void_p,
-                                 C.POINTER(C.c_void_p)]
-    l.go1_vel_bind.argtypes = [C.c_void_p, C.POINTER(VA.Go1VelState), C.POINTER(abi.Go1Plane)]
-    l.go1_vel_set_origins.argtypes = [C.c_void_p, C.c_void_p]
-    l.go1_vel_step.argtypes = [C.c_void_p, C.POINTER(VA.Go1VelStepArgs), C.c_void_p]
-    l.go1_vel_reset_idx.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64,
-                                    C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-    l.go1_vel_resample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
-                                   C.c_void_p]
-    l.go1_vel_destroy.argtypes = [C.c_void_p]
-    if l.go1_vel_abi_version() != VA.GO1_VEL_ABI_VERSION:
-        raise NativeError("velocity ABI version mismatch")
-    _lib = l
-    return l
-
-
-def _check(rc):
-    if rc != 0:
-        raise NativeError(lib().go1_vel_last_error().decode())
+    if _lib is None:
+        _lib = load_library(LIB_PATH, "go1_vel_abi_version", VA.GO1_VEL_ABI_VERSION, "go1_vel_last_error", _ARGTYPES)
+    return _lib
 
 
 # ---------------------------------------------------------------------------- configuration
@@ -263,19 +245,18 @@ def plane_env_origins(n_local, cfg, n_global=None, first=0):
 
 
 # ---------------------------------------------------------------------------- native handle
-class VelNative:
+class VelNative(NativeHandle):
     """Owns one go1_vel_handle, the state planes and the device buffers the C ABI writes."""
+    WHAT = "velocity step"
 
     def __init__(self, phys, vel, grid, w0, device="cuda:0"):
-        if not torch.cuda.is_available():
-            raise NativeError("no GPU visible: the MI355X velocity step has no CPU fallback")
-        self.device = torch.device(device)
+        self._open(device, lib(), lib().go1_vel_destroy)
         self.phys, self.vel = phys, vel
         self.n = n = phys.n_envs
-        self.h = C.c_void_p()
         g = np.ascontiguousarray(grid, np.float64)
         with torch.cuda.device(self.device):
-            _check(lib().go1_vel_create(C.byref(phys), C.byref(vel), g.ctypes.data_as(C.c_void_p), C.byref(self.h)))
+            self._check(self._lib.go1_vel_create(C.byref(phys), C.byref(vel), g.ctypes.data_as(C.c_void_p),
+                                                 C.byref(self.h)))
             self.state = {}
             for name, rows, w, dt in VA.vel_state_spec(vel.n_terms, vel.n_bins):
                 dtype = {"f32": torch.float32, "i32": torch.int32, "f64": torch.float64}[dt]
@@ -287,24 +268,16 @@ class VelNative:
             self.contact_forces = torch.zeros((n, 17, 3), device=dev)
             self.aux = torch.zeros((n, VA.GO1_VEL_AUX), device=dev)
         self._origins = None
-        self._lib_step = lib().go1_vel_step
-        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self._lib_step = self._lib.go1_vel_step
 
     def bind(self, state):
         s = VA.Go1VelState(**{k: state[k].data_ptr() for k, _ in VA.Go1VelState._fields_})
-        arr = (abi.Go1Plane * VA.GO1_VEL_STATE_PLANES)()
-        for i, (name, _) in enumerate(VA.Go1VelState._fields_):
-            t = state[name]
-            shape = tuple(t.shape) + (1,) * (2 - t.dim())
-            stride = tuple(t.stride()) + (1,) * (2 - t.dim())
-            dt = {torch.int32: abi.GO1_DTYPE_I32, torch.float64: VA.GO1_DTYPE_F64}.get(t.dtype, abi.GO1_DTYPE_F32)
-            arr[i] = abi.Go1Plane(rows=shape[0], cols=shape[1], row_stride=stride[0], col_stride=stride[1], dtype=dt)
-        _check(lib().go1_vel_bind(self.h, C.byref(s), arr))
+        self._check(self._lib.go1_vel_bind(self.h, C.byref(s), abi.plane_descs(VA.Go1VelState._fields_, state)))
 
     def set_origins(self, origins):
         t = torch.as_tensor(np.ascontiguousarray(origins, np.float32)).to(self.device)
         self._origins = t
-        _check(lib().go1_vel_set_origins(self.h, C.c_void_p(t.data_ptr())))
+        self._check(self._lib.go1_vel_set_origins(self.h, C.c_void_p(t.data_ptr())))
 
     def args(self):
         a = VA.Go1VelStepArgs()
@@ -315,45 +288,33 @@ class VelNative:
         return a
 
     def step(self, a, stream=None):
-        rc = self._lib_step(self.h, C.byref(a), stream if stream is not None else
-                            torch._C._cuda_getCurrentRawStream(self._dev_index))
+        rc = self._lib_step(self.h, C.byref(a), stream if stream is not None else self._stream())
         if rc:
-            _check(rc)
+            self._check(rc)
 
     def resample(self, mask=None, uniforms=None, uniforms_f64=None, rng_seed=0, rng_step=0):
         m = None if mask is None else mask.to(torch.uint8).contiguous()
-        _check(lib().go1_vel_resample(self.h, None if m is None else m.data_ptr(),
-                                      None if uniforms is None else uniforms.data_ptr(),
-                                      None if uniforms_f64 is None else uniforms_f64.data_ptr(), int(rng_seed),
-                                      int(rng_step), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        self._check(self._lib.go1_vel_resample(self.h, None if m is None else m.data_ptr(),
+                                               None if uniforms is None else uniforms.data_ptr(),
+                                               None if uniforms_f64 is None else uniforms_f64.data_ptr(),
+                                               int(rng_seed), int(rng_step), self._stream()))
         return m
 
     def reset_idx(self, env_ids, uniforms=None, uniforms_f64=None, rng_seed=0, rng_step=0, log=None, log_count=None,
                   log_tag=0):
-        ids = torch.as_tensor(env_ids, device=self.device).to(torch.int32).flatten().contiguous()
-        _check(lib().go1_vel_reset_idx(self.h, ids.data_ptr(), int(ids.numel()),
-                                       None if uniforms is None else uniforms.data_ptr(),
-                                       None if uniforms_f64 is None else uniforms_f64.data_ptr(), int(rng_seed),
-                                       int(rng_step), None if log is None else log.data_ptr(),
-                                       None if log_count is None else log_count.data_ptr(),
-                                       0 if log is None else int(log.shape[0]), int(log_tag),
-                                       C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        ids = self._ids(env_ids)
+        self._check(self._lib.go1_vel_reset_idx(self.h, ids.data_ptr(), int(ids.numel()),
+                                                None if uniforms is None else uniforms.data_ptr(),
+                                                None if uniforms_f64 is None else uniforms_f64.data_ptr(),
+                                                int(rng_seed), int(rng_step), None if log is None else log.data_ptr(),
+                                                None if log_count is None else log_count.data_ptr(),
+                                                0 if log is None else int(log.shape[0]), int(log_tag),
+                                                self._stream()))
         return ids
-
-    def close(self):
-        if self.h:
-            lib().go1_vel_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---------------------------------------------------------------------------- the env
-class VelocityTrackingEasyEnv:
+class VelocityTrackingEasyEnv(EnvBase):
     """VelocityTrackingEasyEnv (velocity_tracking/__init__.py:11-55) for scripts/train_velocity_tracking.py's
     configuration on a plane (BASELINE configs[1]), backed by the HIP step."""
 
@@ -366,144 +327,43 @@ class VelocityTrackingEasyEnv:
             cfg = V.train_velocity_config(n_envs=num_envs or 4096)
         if num_envs is not None:
             cfg.env.num_envs = num_envs
-        if rank is None or world_size is None:
-            from .env import _dist_info
-            r, w = _dist_info()
-            rank = r if rank is None else rank
-            world_size = w if world_size is None else world_size
-        self.rank, self.world_size = rank, world_size
-        self.cfg = cfg
-        self.eval_cfg = None
-        self.sim_device = sim_device
-        self.headless = headless
-        self.num_obs = int(cfg.env.num_observations)
-        self.num_privileged_obs = int(cfg.env.num_privileged_obs)
-        self.num_actions = int(cfg.env.num_actions)
-        self.num_envs = self.num_train_envs = n = int(cfg.env.num_envs)
-        self.num_eval_envs = 0
-        self.seed = int(seed)
-        d = V.vel_derived(cfg)
-        self.dt = d["dt"]
-        self.max_episode_length = d["max_episode_length"]
-        self._gravity_interval = d["gravity_rand_interval"]
-        self._gravity_duration = d["gravity_rand_duration"]
+        self._init_dims(cfg, V.vel_derived(cfg), sim_device, headless, seed, rank, world_size)
+        rank, n = self.rank, self.num_envs
         self._phys, self._vcfg, grid, w0, self.reward_names, self.command_sum_keys = build_configs(
             cfg, n_envs=n, physics=physics, env_id_offset=rank * n)
-        self.reward_scales = dict(d["reward_scales"])
         self.episode_keys = list(self.reward_names) + ["total"]
         self.curriculum_grid = grid
         self.category_names = list(V.CATEGORIES) if cfg.commands.gaitwise_curricula else ["nominal"]
         self._sim = VelNative(self._phys, self._vcfg, grid, w0, sim_device)
         self.device = dev = self._sim.device
-        self._n_global = n * world_size
         self.env_origins = torch.as_tensor(plane_env_origins(n, cfg, self._n_global, rank * n), device=dev)
         self._sim.set_origins(self.env_origins.cpu().numpy())
+        # rings, creation-time DR and the gravity defaults: Cfg.sim.gravity until the first scheduled draw
+        # (:719-723, no draw at creation), projection vector -z (:1186)
+        self._init_host_state()
         st = self._sim.state
-        # _init_buffers / _randomize_rigid_body_props at creation: per-env DR keyed by GLOBAL env id
-        dr = cfg.domain_rand
-        st["friction"].copy_(self._global_uniform(1, *dr.friction_range) if dr.randomize_friction else
-                             torch.ones((n, 1), device=dev))
-        if dr.randomize_restitution:
-            st["restitution"].copy_(self._global_uniform(2, *dr.restitution_range))
-        if dr.randomize_base_mass:
-            st["payload"].copy_(self._global_uniform(3, *dr.added_mass_range))
-        st["motor_strength"].fill_(1.0)
         st["root"][:, 6] = 1.0
         st["root"][:, :3] = self.env_origins + torch.as_tensor(list(cfg.init_state.pos), device=dev)
         for i, nme in enumerate(L.DOF_NAMES):
             st["dof_pos"][:, i] = float(cfg.init_state.default_joint_angles[nme])
-        # outputs
-        self._obs = torch.zeros((OUT_RING, n, self.num_obs), device=dev)
-        self._priv = torch.zeros((OUT_RING, n, self.num_privileged_obs), device=dev)
-        self._rew = torch.zeros((OUT_RING, n), device=dev)
-        self._reset = torch.zeros((OUT_RING, n), dtype=torch.bool, device=dev)
-        self._time_out = torch.zeros((OUT_RING, n), dtype=torch.bool, device=dev)
-        self._slot = 0
         self._hist = None  # 2 wide (n, 70 x (history + HIST_WINDOW)) buffers when a HistoryWrapper attaches
         self._hist_buf, self._hist_off = 0, 0  # buffer and window (in observations) of the last returned history
-        self._last_hist = None
         # compact episode log: one row per reset env (n_terms + 1 sums, tag, env)
         self._log_cap = max(4 * n, 1024)
         self._log = torch.zeros((self._log_cap, len(self.episode_keys) + 2), device=dev)
         self._log_count = torch.zeros(1, dtype=torch.int32, device=dev)
         self._log_tag = 0
-        # gravity: Cfg.sim.gravity until the first scheduled draw (:719-723); projection vector -z (:1186)
-        self.common_step_counter = 0
-        self.gravities = np.zeros(3, np.float32)
-        self._sim_gravity = np.asarray(cfg.sim.gravity, np.float32)
-        self._gravity_vec = np.array([0.0, 0.0, -1.0], np.float32)
-        self._host_rng = np.random.default_rng(self.seed)
-        self._rng_step = 0
         self._args = [None] * OUT_RING
         self._args_grav = [None] * OUT_RING  # per output slot: the gravity versions / reward scales its args hold
         self._args_rs = [None] * OUT_RING
-        self._grav_version = 0
-        self._gravity_interval_i = int(self._gravity_interval)
         self.extras = self._make_extras()
-        self.kernel_events = deque()
         # the first step's interval resample (none unless episode lengths were set)
         self._sim.resample(None, rng_seed=self.seed, rng_step=self._rng_step)
 
-    # ---------------------------------------------------------------- host state
-    def _global_uniform(self, tag, lo, hi):
-        u = np.random.Generator(np.random.Philox(key=[self.seed, tag])).random(self._n_global).astype(np.float32)
-        u = u[self.rank * self.num_envs:(self.rank + 1) * self.num_envs, None]
-        return torch.from_numpy(u * np.float32(hi - lo) + np.float32(lo)).to(self.device)
-
-    def _randomize_gravity(self, external_force=None):
-        """_randomize_gravity (:564-579): one global draw shared by every env (and rank)."""
-        if external_force is not None:
-            self.gravities[:] = np.asarray(external_force, np.float32)
-        elif self.cfg.domain_rand.randomize_gravity:
-            lo, hi = self.cfg.domain_rand.gravity_range
-            u = self._host_rng.random(3).astype(np.float32)
-            self.gravities[:] = u * np.float32(hi - lo) + np.float32(lo)
-        self._sim_gravity, self._gravity_vec = CF.gravity_state(self.gravities)
-        self._grav_version += 1
-
-    @property
-    def state(self):
-        return self._sim.state
-
-    @property
-    def obs_buf(self):
-        return self._obs[(self._slot - 1) % OUT_RING]
-
-    @property
-    def privileged_obs_buf(self):
-        return self._priv[(self._slot - 1) % OUT_RING]
-
-    @property
-    def rew_buf(self):
-        return self._rew[(self._slot - 1) % OUT_RING]
-
-    @property
-    def reset_buf(self):
-        return self._reset[(self._slot - 1) % OUT_RING]
-
-    @property
-    def time_out_buf(self):
-        return self._time_out[(self._slot - 1) % OUT_RING]
-
-    @property
-    def episode_length_buf(self):
-        return self._sim.state["episode_length"][:, 0]
-
+    # ---------------------------------------------------------------- views
     @property
     def commands(self):
         return self._sim.state["commands"]
-
-    @property
-    def root_states(self):
-        return self._sim.state["root"]
-
-    @property
-    def dof_pos(self):
-        return self._sim.state["dof_pos"]
-
-    @property
-    def dof_vel(self):
-        return self._sim.state["dof_vel"]
 
     @property
     def base_lin_vel(self):
@@ -528,12 +388,6 @@ class VelocityTrackingEasyEnv:
     @property
     def contact_forces(self):
         return self._sim.contact_forces
-
-    def get_observations(self):
-        return self.obs_buf
-
-    def get_privileged_observations(self):
-        return self.privileged_obs_buf
 
     # ---------------------------------------------------------------- history (HistoryWrapper fusion)
     def attach_history(self, length):
@@ -573,15 +427,7 @@ class VelocityTrackingEasyEnv:
     # ---------------------------------------------------------------- step
     def step(self, actions, history_in=None):
         """VelocityTrackingEasyEnv.step (__init__.py:22-44): obs, rew, reset, extras."""
-        a = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(actions)
-        if a.device != self.device or a.dtype != torch.float32:
-            a = a.to(self.device, torch.float32)
-        if a.requires_grad:
-            a = a.detach()
-        if not a.is_contiguous():
-            a = a.contiguous()
-        if a.shape != (self.num_envs, self.num_actions):
-            raise ValueError(f"actions must be ({self.num_envs}, {self.num_actions}), got {tuple(a.shape)}")
+        a = self._as_actions(actions)
         s = self._slot
         args = self._args[s]
         if args is None:
@@ -594,13 +440,7 @@ class VelocityTrackingEasyEnv:
         # before this step's schedule, orientation_control the one after, the physics the sim gravity before
         # (_randomize_gravity replaces the arrays, so these references keep the values before it)
         gvec, sgrav, vb = self._gravity_vec, self._sim_gravity, self._grav_version
-        self.common_step_counter += 1
-        c = self.common_step_counter
-        gi = self._gravity_interval_i
-        if c % gi == 0:
-            self._randomize_gravity()
-        if int(c - self._gravity_duration) % gi == 0:
-            self._randomize_gravity(np.zeros(3, np.float32))
+        self._tick_gravity_schedule()
         args.actions = a.data_ptr()
         # the args of an output slot are rewritten only where they changed since that slot's last step
         gkey = (vb, self._grav_version)
@@ -637,23 +477,12 @@ class VelocityTrackingEasyEnv:
     def _make_extras(self):
         """The env's extras dict, built once: the VelocityTrackingEasyEnv.step numpy extras (:25-41) and
         reset_idx's "train/episode" are computed when read (no device->host copy per step)."""
-        from .env import StepExtras
         ex = StepExtras(self)
         ex.set_lazy("time_outs", lambda: self._sim.extras_time_outs[: self.num_train_envs])
         ex.set_lazy("train/episode", self._episode_extras)
-        ex.set_lazy("joint_pos", lambda: self.dof_pos.cpu().numpy())
-        ex.set_lazy("joint_vel", lambda: self.dof_vel.cpu().numpy())
-        ex.set_lazy("joint_pos_target", lambda: self.joint_pos_target.cpu().numpy())
-        dict.__setitem__(ex, "joint_vel_target", torch.zeros(12))
-        ex.set_lazy("body_linear_vel", lambda: self.base_lin_vel.cpu().numpy())
-        ex.set_lazy("body_angular_vel", lambda: self.base_ang_vel.cpu().numpy())
-        ex.set_lazy("body_linear_vel_cmd", lambda: self.commands.cpu().numpy()[:, 0:2])
-        ex.set_lazy("body_angular_vel_cmd", lambda: self.commands.cpu().numpy()[:, 2:])
-        ex.set_lazy("contact_states",
-                    lambda: (self.contact_forces[:, list(L.FEET_INDICES), 2] > 1.0).cpu().numpy().copy())
-        ex.set_lazy("foot_positions", lambda: self.foot_positions.cpu().numpy().copy())
-        ex.set_lazy("body_pos", lambda: self.root_states[:, 0:3].cpu().numpy())
-        ex.set_lazy("torques", lambda: self.torques.cpu().numpy())
+        self._install_step_extras(ex, body_linear_vel_cmd=lambda: self.commands.cpu().numpy()[:, 0:2],
+                                  body_angular_vel_cmd=lambda: self.commands.cpu().numpy()[:, 2:],
+                                  body_pos=lambda: self.root_states[:, 0:3].cpu().numpy())
         return ex
 
     def _flush_episode_log(self):
@@ -694,12 +523,9 @@ class VelocityTrackingEasyEnv:
 
     def reset_idx(self, env_ids):
         """reset_idx (:168-257) for explicit ids (the step resets its own envs in the kernel)."""
-        env_ids = torch.as_tensor(env_ids, device=self.device).long().flatten()
-        if env_ids.numel() == 0:
+        env_ids = self._norm_env_ids(env_ids)
+        if env_ids is None:
             return
-        if int(env_ids.min()) < -self.num_envs or int(env_ids.max()) >= self.num_envs:
-            raise IndexError(f"env id out of range for {self.num_envs} envs")
-        env_ids = torch.remainder(env_ids, self.num_envs)
         self._log_tag += 1
         self._sim.reset_idx(env_ids, rng_seed=self.seed, rng_step=(1 << 62) + self._rng_step, log=self._log,
                             log_count=self._log_count, log_tag=self._log_tag)
@@ -711,31 +537,3 @@ class VelocityTrackingEasyEnv:
         self.reset_idx(torch.arange(self.num_envs, device=self.device))
         obs, _, _, _ = self.step(torch.zeros(self.num_envs, self.num_actions, device=self.device))
         return obs
-
-    # ---------------------------------------------------------------- misc API
-    def start_recording(self):
-        pass
-
-    def pause_recording(self):
-        pass
-
-    def start_recording_eval(self):
-        pass
-
-    def pause_recording_eval(self):
-        pass
-
-    def get_complete_frames(self):
-        return []
-
-    def get_complete_frames_eval(self):
-        return []
-
-    def render(self, mode="rgb_array"):
-        return None
-
-    def close(self):
-        self._sim.close()
-
-
-del math
