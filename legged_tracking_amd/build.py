@@ -28,6 +28,8 @@ LIBS = {
                            ["pmath.h", "go1_device.h", "go1_step_shared.h", "go1_model_consts.h",
                             os.path.join(INC, "go1_mi355x.h"), os.path.join(INC, "go1_velocity.h")],
                            STEP_FLAGS + ["-mllvm", "-amdgpu-kernarg-preload-count=16"]),
+    # the ray caster behind the recording API (render.py); it shares no file with the step libraries
+    "libgo1_render.so": (["go1_render.hip"], [os.path.join(INC, "go1_render.h")], []),
 }
 OUT = os.path.join(BUILD, "libgo1_mi355x.so")  # the step library (kept for callers of build())
 

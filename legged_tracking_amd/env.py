@@ -454,6 +454,8 @@ class LeggedRobot(EnvBase):
                            rng_step=self._rng_step, out=out, episode_log=self._elog.next_slot(),
                            aux=self._aux if self._demand[1] else None, obs_history=hist, events=events,
                            diverged_count=self._diverged, **cf)
+        if self._rec is not None:  # a recording is armed: its launch follows the step kernel on the same stream
+            self._record_step(out["reset"])
         self._last_hist = hist
         self._rng_step += 1
         self._elog.advance()

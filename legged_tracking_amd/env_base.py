@@ -3,7 +3,7 @@
 EnvBase owns the rank / world-size resolution, dims and seed, the OUT_RING output rings with their *_buf
 views, the state views, the per-env Philox draws keyed by global env id (creation-time domain
 randomisation), the global gravity schedule (_randomize_gravity, _tick_gravity_schedule), the action and
-env-id normalisation, the twelve lazy numpy extras and the reference's recording / render stubs.
+env-id normalisation, the twelve lazy numpy extras and the reference's recording / render surface (render.py).
 
 Each env keeps what differs: when its step ticks the gravity schedule (after the launch / before it, with
 the pre- and post-tick vectors), the initial gravity draw (trajectory only), its aux column layout,
@@ -254,11 +254,39 @@ class EnvBase:
         ex.set_lazy("torques", lambda: self.torques.cpu().numpy())
 
     # ------------------------------------------------------------------ misc API
+    # ------------------------------------------------------------------ recording and rendering (render.py)
+    # legged_robot_trajectory_tracking.py:1690-1711, :1775-1806.  Nothing is allocated or launched until the first
+    # start_recording / render call; while a recording is armed, step() issues one recording launch after the step
+    # kernel (_record_step), which reads the state planes and the step's reset output only.
+    renderer_factory = None  # tests inject a test double; None: render.Renderer
+    _renderer = None         # created on first use
+    _rec = None              # the renderer while record_now is set (:1777), else None
+
+    def _get_renderer(self):
+        if self._renderer is None:
+            factory = self.renderer_factory
+            if factory is None:
+                from . import render
+                factory = render.Renderer
+            self._renderer = factory(self)
+        return self._renderer
+
+    def _records(self):
+        """Only the rank that owns global env 0 records; the others keep the surface's empty answers."""
+        return self.rank == 0
+
+    def _record_step(self, reset):
+        self._rec.record_step(reset)
+
     def start_recording(self):
-        pass
+        if self._records():
+            self._rec = self._get_renderer()
+            self._rec.start()
 
     def pause_recording(self):
-        pass
+        if self._renderer is not None:
+            self._renderer.pause()
+        self._rec = None
 
     def start_recording_eval(self):
         pass
@@ -267,13 +295,30 @@ class EnvBase:
         pass
 
     def get_complete_frames(self):
-        return []
+        """[] until the recorded episode of env 0 is complete, then its (240, 360, 4) uint8 frames."""
+        return self._renderer.complete_frames() if self._renderer is not None else []
 
     def get_complete_frames_eval(self):
         return []
 
     def render(self, mode="rgb_array"):
-        return None
+        """render (:1690-1699): env 0 from the follow camera, (240, 360, 4) uint8; None on the ranks that do not own
+        global env 0."""
+        assert mode == "rgb_array"
+        if not self._records():
+            return None
+        from . import render as R
+        r = self._get_renderer()
+        return r.render((0,), r.width, r.height, R.MODE_FOLLOW, R.VIEW_NO_CEILING)[0]
+
+    def render_all_envs(self):
+        """render_all_envs (:1701-1711): one (recording_height_px, recording_width_px, 4) frame per env with the
+        video camera's mode, or None unless cfg.env.record_all_envs."""
+        e = self.cfg.env
+        if not getattr(e, "record_all_envs", False):
+            return None
+        frames = self._get_renderer().render(tuple(range(self.num_envs)), e.recording_width_px, e.recording_height_px)
+        return list(frames)
 
     def close(self):
         self._sim.close()

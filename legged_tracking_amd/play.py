@@ -1,0 +1,92 @@
+"""python -m legged_tracking_amd.play LOGDIR --out DIR [--steps 500] [--envs 16] [--width 640] [--height 480]
+
+What the reference's scripts/eval.py:68-173 does, without the plots: load a Runner checkpoint (LOGDIR/ac_weights.pt
+or LOGDIR/checkpoints/ac_weights.pt; the Cfg of LOGDIR/parameters.pkl when it is there), build a 4 x 4 tunnel grid
+with the domain randomisation switched off and record_all_envs on, run the policy and write one GIF per env
+(env_{i}.gif; .npy without PIL) from render_all_envs()."""
+import argparse
+import os
+import pickle
+
+import numpy as np
+import torch
+
+from . import config as CF, video
+from .env import HistoryWrapper, TrajectoryTrackingEnv
+from .rollout import ActorCritic
+
+# scripts/eval.py:89-101
+DR_OFF = ("push_robots", "randomize_friction", "randomize_gravity", "randomize_restitution", "randomize_motor_offset",
+          "randomize_motor_strength", "randomize_friction_indep", "randomize_ground_friction", "randomize_base_mass",
+          "randomize_Kd_factor", "randomize_Kp_factor", "randomize_joint_friction", "randomize_com_displacement")
+
+
+def _find(logdir, name):
+    for p in (os.path.join(logdir, name), os.path.join(logdir, "checkpoints", name)):
+        if os.path.exists(p):
+            return p
+    return None
+
+
+def load_cfg(logdir, n_envs, width, height):
+    """readme_config on a 4 x 4 grid, overridden by parameters.pkl ({section: {key: value}}) and then by
+    eval.py's play settings (:82-101)."""
+    # a 4 x 4 grid (:87-88); fewer than 16 envs get the largest square grid that their number fills evenly
+    g = max(k for k in (1, 2, 3, 4) if n_envs % (k * k) == 0)
+    cfg = CF.readme_config(n_envs=n_envs, terrain="single_path", rows=g, cols=g)
+    pkl =_find(logdir, "parameters.pkl")
+    if pkl is not None:
+        with open(pkl, "rb") as f:
+            saved = pickle.load(f)
+        for section, values in saved.items():
+            if hasattr(cfg, section) and isinstance(values, dict):
+                for k, v in values.items():
+                    setattr(getattr(cfg, section), k, v)
+    e = cfg.env
+    e.recording_width_px, e.recording_height_px = int(width), int(height)
+    e.num_envs, e.look_from_back, e.record_all_envs = int(n_envs), True, True
+    cfg.terrain.num_rows = cfg.terrain.num_cols = g
+    for k in DR_OFF:
+        setattr(cfg.domain_rand, k, False)
+    return cfg
+
+
+def play(logdir, out, steps=500, envs=16, width=640, height=480, device="cuda:0", seed=11):
+    """Returns the files written, one per env."""
+    weights = _find(logdir, "ac_weights.pt")
+    if weights is None:
+        raise FileNotFoundError(f"no ac_weights.pt under {logdir}")
+    envs = int(envs)
+    n_built = -(-envs // 16) * 16  # the HIP step takes multiples of 16 envs; the first `envs` are written
+    cfg = load_cfg(logdir, n_built, width, height)
+    env = HistoryWrapper(TrajectoryTrackingEnv(sim_device=device, headless=True, cfg=cfg, seed=seed))
+    ac = ActorCritic(env.num_obs, env.num_privileged_obs, env.num_obs_history, env.num_actions).to(env.device)
+    ac.load_state_dict(torch.load(weights, map_location=env.device, weights_only=True))
+    ac.eval()
+    obs = env.reset()
+    frames = []
+    with torch.no_grad():
+        for _ in range(int(steps)):
+            obs, _, _, _ = env.step(ac.act(obs["obs_history"]))
+            frames.append(np.stack(env.render_all_envs()[:envs]))
+    env.close()
+    per_env = np.stack(frames).transpose(1, 0, 2, 3, 4)  # (env, step, H, W, 4)
+    return [video.save_frames(f, os.path.join(out, f"env_{i}.gif"), fps=1 / env.dt) for i, f in enumerate(per_env)]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("logdir")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--steps", type=int, default=500)
+    ap.add_argument("--envs", type=int, default=16)
+    ap.add_argument("--width", type=int, default=640)
+    ap.add_argument("--height", type=int, default=480)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    for p in play(a.logdir, a.out, a.steps, a.envs, a.width, a.height, a.device):
+        print(p)
+
+
+if __name__ == "__main__":
+    main()

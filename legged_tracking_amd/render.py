@@ -1,0 +1,299 @@
+"""Host binding of the ray caster (include/go1_render.h, legged_tracking_amd/_build/libgo1_render.so) and the
+recorder behind the envs' start_recording / get_complete_frames / render surface (env_base.py).
+
+The picture is the collision scene: the capsules, the foot spheres and the trunk box the contact code collides with,
+posed from the live state planes, on the env's terrain tile as the triangle mesh the contact model uses.  torch
+provides the device memory and the stream; every pixel is computed by the HIP kernel (no CPU fallback).
+
+Renderer keeps the reference's frame lists on the device: a frame ring of (max_episode_length + 1, 240, 360, 4)
+bytes and a state record the recording launch advances itself (go1_render_record), so a recorded step costs one
+launch and no device->host copy; get_complete_frames reads the record (a few bytes) when it is called and copies
+the finished episode to the host once."""
+import ctypes as C
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import layout as L, model as M
+from .native import NativeError, check, load_library
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(HERE, "_build", "libgo1_render.so")
+GO1_RENDER_ABI_VERSION = 1
+MAX_MARKERS = 8
+PRIM_TRUNK, PRIM_FLOOR, PRIM_CEILING, PRIM_MARKER, PRIM_BACKGROUND = 16, 17, 18, 19, -1
+VIEW_NO_CEILING = 1
+MODE_LOOK_FROM_BACK, MODE_FOLLOW, MODE_EXPLICIT = 0, 1, 2
+REC_IDLE, REC_ARMED, REC_RECORDING, REC_COMPLETE = 0, 1, 2, 3
+VIDEO_WIDTH, VIDEO_HEIGHT = 360, 240   # camera_props of the video camera (legged_robot_trajectory_tracking.py:1667-1669)
+WAYPOINT_RADIUS = 0.04
+
+F, I32, P = C.c_float, C.c_int32, C.c_void_p
+
+
+class Go1RenderModel(C.Structure):
+    _fields_ = [("hip_origin", F * 3 * 4), ("thigh_origin", F * 3 * 4), ("calf_origin", F * 3), ("foot_offset", F * 3),
+                ("hip_capsule_y", F * 2 * 4), ("thigh_radius", F), ("hip_radius", F), ("calf_radius", F),
+                ("foot_radius", F), ("trunk_half", F * 3), ("bound_radius", F)]
+
+
+class Go1RenderView(C.Structure):
+    _fields_ = [("env", I32), ("mode", I32), ("flags", I32), ("pad", I32), ("pos", F * 3), ("look_at", F * 3)]
+
+
+class Go1RenderArgs(C.Structure):
+    _fields_ = [("model", Go1RenderModel), ("root", P), ("dof_pos", P), ("tiles", P), ("env_tile", P),
+                ("env_terrain_origin", P), ("markers", P), ("wp_trajectory", P), ("wp_index", P), ("views", P),
+                ("rgba", P), ("depth", P), ("prim_id", P),
+                ("n_envs", I32), ("n_tiles", I32), ("hf_nx", I32), ("hf_ny", I32), ("n_markers", I32),
+                ("wp_length", I32), ("n_views", I32), ("width", I32), ("height", I32),
+                ("horizontal_scale", F), ("wp_radius", F), ("pad", I32)]
+
+
+class Go1RecordArgs(C.Structure):
+    _fields_ = [("r", Go1RenderArgs), ("reset", P), ("state", P), ("capacity", I32), ("pad", I32),
+                ("step", C.c_uint64)]
+
+
+_ARGTYPES = {
+    "go1_render_abi_sizes": [C.POINTER(C.c_int64)],
+    "go1_render": [C.POINTER(Go1RenderArgs), C.c_void_p],
+    "go1_render_record": [C.POINTER(Go1RecordArgs), C.c_void_p],
+}
+_lib = None
+
+
+def lib():
+    """The render library, loaded once."""
+    global _lib
+    if _lib is None:
+        _lib = load_library(LIB_PATH, "go1_render_abi_version", GO1_RENDER_ABI_VERSION, "go1_render_last_error",
+                            _ARGTYPES)
+    return _lib
+
+
+def model_struct():
+    """go1_render_model from model.py: the geometry tests/self_geom.py restates."""
+    m = Go1RenderModel()
+    reach = 0.0
+    for l, leg in enumerate(L.LEGS):
+        hip, thigh, calf = M.joint_origins(leg)
+        sy = M.LEG_SIGNS[leg][1]
+        m.hip_origin[l][:] = hip
+        m.thigh_origin[l][:] = thigh
+        m.hip_capsule_y[l][:] = [sy * M.HIP_CAPSULE_Y[0], sy * M.HIP_CAPSULE_Y[1]]
+        reach = max(reach, math.sqrt(sum(x * x for x in hip)) + math.sqrt(sum(x * x for x in thigh)) +
+                    abs(M.HIP_CAPSULE_Y[1]))
+    m.calf_origin[:] = M.CALF_OFFSET
+    m.foot_offset[:] = M.FOOT_OFFSET
+    m.thigh_radius, m.hip_radius = M.THIGH_BOX_HALF_WIDTH, M.HIP_CAPSULE_RADIUS
+    m.calf_radius, m.foot_radius = M.CALF_BOX_HALF_WIDTH, M.FOOT_RADIUS
+    m.trunk_half[:] = [x / 2 for x in M.TRUNK_BOX]
+    chain = math.sqrt(sum(x * x for x in M.CALF_OFFSET)) + math.sqrt(sum(x * x for x in M.FOOT_OFFSET))
+    trunk = math.sqrt(sum((x / 2) ** 2 for x in M.TRUNK_BOX))
+    m.bound_radius = 1.01 * max(trunk, reach + chain + max(M.HIP_CAPSULE_RADIUS, M.THIGH_BOX_HALF_WIDTH,
+                                                            M.CALF_BOX_HALF_WIDTH, M.FOOT_RADIUS))
+    return m
+
+
+def views_tensor(views, device):
+    """Device copy of go1_render_view records.  `views`: (env, mode[, flags[, pos, look_at]]) tuples."""
+    arr = (Go1RenderView * len(views))()
+    for v, rec in zip(arr, views):
+        v.env, v.mode = int(rec[0]), int(rec[1])
+        v.flags = int(rec[2]) if len(rec) > 2 else 0
+        if len(rec) > 3:
+            v.pos[:] = [float(x) for x in rec[3]]
+            v.look_at[:] = [float(x) for x in rec[4]]
+    return torch.from_numpy(np.frombuffer(bytes(arr), np.uint8).copy()).to(device)
+
+
+class Scene:
+    """What a launch reads: the state planes, the terrain and the optional waypoint planes (tensors on one device,
+    kept alive here)."""
+
+    def __init__(self, root, dof_pos, tiles=None, env_tile=None, env_terrain_origin=None, horizontal_scale=0.1,
+                 trajectory=None, curr_pose_index=None):
+        self.root, self.dof_pos = root, dof_pos
+        self.tiles, self.env_tile, self.env_terrain_origin = tiles, env_tile, env_terrain_origin
+        self.hs = float(horizontal_scale)
+        self.trajectory, self.curr_pose_index = trajectory, curr_pose_index
+        n = root.shape[0]
+        for name, t, shape, dt in (("root", root, (n, 13), torch.float32), ("dof_pos", dof_pos, (n, 12), torch.float32)):
+            _dense(name, t, shape, dt)
+        if tiles is not None:
+            if tiles.dim() != 4 or tiles.shape[1] != 2:
+                raise NativeError("tiles must be (n_tiles, 2, hf_nx, hf_ny)")
+            _dense("tiles", tiles, tuple(tiles.shape), torch.float32)
+            _dense("env_tile", env_tile, (n,), torch.int32)
+            _dense("env_terrain_origin", env_terrain_origin, (n, 3), torch.float32)
+        if trajectory is not None:
+            if trajectory.dim() != 2 or trajectory.shape[1] % 6:
+                raise NativeError("trajectory must be (n_envs, 6 x length)")
+            _dense("trajectory", trajectory, (n, trajectory.shape[1]), torch.float32)
+            _dense("curr_pose_index", curr_pose_index, (n, 1), torch.int32)
+
+    def fill(self, a):
+        a.model = model_struct()
+        a.root, a.dof_pos, a.n_envs = self.root.data_ptr(), self.dof_pos.data_ptr(), int(self.root.shape[0])
+        a.horizontal_scale = self.hs
+        if self.tiles is not None:
+            a.tiles, a.env_tile = self.tiles.data_ptr(), self.env_tile.data_ptr()
+            a.env_terrain_origin = self.env_terrain_origin.data_ptr()
+            a.n_tiles, a.hf_nx, a.hf_ny = (int(x) for x in (self.tiles.shape[0], self.tiles.shape[2],
+                                                           self.tiles.shape[3]))
+        if self.trajectory is not None:
+            a.wp_trajectory, a.wp_index = self.trajectory.data_ptr(), self.curr_pose_index.data_ptr()
+            a.wp_length, a.wp_radius = int(self.trajectory.shape[1] // 6), WAYPOINT_RADIUS
+
+
+def _dense(name, t, shape, dtype):
+    if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
+        raise NativeError(f"{name} must be a contiguous {tuple(shape)} {dtype} tensor")
+
+
+def _stream(device):
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    return torch._C._cuda_getCurrentRawStream(idx)
+
+
+def render_views(scene, views, width, height, markers=None, depth=False, prim_id=False, out=None):
+    """One go1_render launch on the current stream: `views` is a views_tensor; returns rgba (n_views, H, W, 4)
+    uint8, then depth (f32) and prim_id (int32) when asked for.  `markers`: (n_views, m, 4) f32 or None."""
+    dev = scene.root.device
+    if dev.type != "cuda":
+        raise NativeError("no GPU visible: the MI355X ray caster has no CPU fallback")
+    nv = views.numel() // C.sizeof(Go1RenderView)
+    a = Go1RenderArgs()
+    scene.fill(a)
+    a.views, a.n_views, a.width, a.height = views.data_ptr(), nv, int(width), int(height)
+    rgba = out if out is not None else torch.empty((nv, height, width, 4), dtype=torch.uint8, device=dev)
+    _dense("rgba", rgba, (nv, height, width, 4), torch.uint8)
+    res = [rgba]
+    a.rgba = rgba.data_ptr()
+    if markers is not None:
+        _dense("markers", markers, (nv, markers.shape[1], 4), torch.float32)
+        a.markers, a.n_markers = markers.data_ptr(), int(markers.shape[1])
+    if depth:
+        res.append(torch.empty((nv, height, width), dtype=torch.float32, device=dev))
+        a.depth = res[-1].data_ptr()
+    if prim_id:
+        res.append(torch.empty((nv, height, width), dtype=torch.int32, device=dev))
+        a.prim_id = res[-1].data_ptr()
+    with torch.cuda.device(dev):
+        check(lib(), lib().go1_render(C.byref(a), _stream(dev)))
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+class Renderer:
+    """The recorder of one env (EnvBase creates it at the first start_recording / render call)."""
+
+    def __init__(self, env):
+        self.env = env
+        self.device = env.device
+        self.capacity = int(env.max_episode_length) + 1
+        self.width, self.height = VIDEO_WIDTH, VIDEO_HEIGHT
+        self.frames = self.state = None
+        self.step = 0
+        self._complete = None
+        self._views = {}
+        self._scene = None
+        self._args = None
+
+    # ------------------------------------------------------------------ scene and views
+    def camera(self):
+        """(mode, flags) of the video camera: look_from_back, or the follow camera, which sits above the tunnel and
+        therefore leaves the ceiling out."""
+        if getattr(self.env.cfg.env, "look_from_back", False):
+            return MODE_LOOK_FROM_BACK, 0
+        return MODE_FOLLOW, VIEW_NO_CEILING
+
+    def scene(self):
+        if self._scene is None:
+            env = self.env
+            st = env._sim.state
+            kw = dict(horizontal_scale=float(getattr(env.cfg.terrain, "horizontal_scale", 0.1)))
+            keep = getattr(env._sim, "_terrain_keep", None)
+            if keep is not None and getattr(getattr(env, "terrain", None), "kind", "plane") != "plane":
+                kw.update(tiles=keep[0], env_tile=keep[1], env_terrain_origin=keep[2])
+            try:
+                kw.update(trajectory=st["trajectory"], curr_pose_index=st["curr_pose_index"])
+            except KeyError:  # the velocity env has no waypoints
+                pass
+            self._scene = Scene(st["root"], st["dof_pos"], **kw)
+        return self._scene
+
+    def views(self, envs, mode, flags):
+        key = (tuple(envs), mode, flags)
+        v = self._views.get(key)
+        if v is None:
+            v = self._views[key] = views_tensor([(e, mode, flags) for e in envs], self.device)
+        return v
+
+    def render(self, envs, width, height, mode=None, flags=None):
+        """(len(envs), height, width, 4) uint8 numpy frames of the current state."""
+        m, f = self.camera()
+        mode, flags = m if mode is None else mode, f if flags is None else flags
+        return self._render_launch(self.views(envs, mode, flags), int(width), int(height)).cpu().numpy()
+
+    # ------------------------------------------------------------------ recording
+    def _state_const(self, s):
+        return torch.tensor([[s, 0, 0, 0], [s, 0, 0, 0]], dtype=torch.int32).to(self.device)
+
+    def start(self):
+        """start_recording (:1775-1777): armed, the next reset of env 0 starts the episode."""
+        if self.frames is None:
+            self.frames = torch.zeros((self.capacity, self.height, self.width, 4), dtype=torch.uint8,
+                                      device=self.device)
+            self.state = torch.zeros((2, 4), dtype=torch.int32, device=self.device)
+            self._consts = {s: self._state_const(s) for s in (REC_IDLE, REC_ARMED)}
+        self.state.copy_(self._consts[REC_ARMED])
+        self._complete = None
+
+    def pause(self):
+        """pause_recording (:1783-1787): the lists are emptied and nothing is drawn until the next start."""
+        if self.state is not None:
+            self.state.copy_(self._consts[REC_IDLE])
+        self._complete = None
+
+    def record_step(self, reset):
+        """The recording launch of one env step, after the step kernel on its stream; `reset` is the step's
+        reset output."""
+        self._record_launch(reset, self.step)
+        self.step += 1
+
+    def complete_frames(self):
+        """get_complete_frames (:1795-1799): [] until the recorded episode is complete, then its frames."""
+        if self.state is None:
+            return []
+        st, count = (int(x) for x in self.state[self.step & 1, :2].tolist())
+        if st != REC_COMPLETE:
+            return []
+        if self._complete is None:
+            self._complete = list(self.frames[:count].cpu().numpy())
+        return self._complete
+
+    # ------------------------------------------------------------------ launches (a test double replaces these two)
+    def _render_launch(self, views, width, height):
+        return render_views(self.scene(), views, width, height)
+
+    def _record_launch(self, reset, step):
+        a = self._args
+        if a is None:
+            a = self._args = Go1RecordArgs()
+            self.scene().fill(a.r)
+            mode, flags = self.camera()
+            v = self.views((0,), mode, flags)
+            a.r.views, a.r.n_views, a.r.width, a.r.height = v.data_ptr(), 1, self.width, self.height
+            a.r.rgba, a.state, a.capacity = self.frames.data_ptr(), self.state.data_ptr(), self.capacity
+            self._lib_record = lib().go1_render_record
+            self._stream_of = torch._C._cuda_getCurrentRawStream
+            self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        if reset.dtype != torch.bool or reset.shape != (a.r.n_envs,) or not reset.is_contiguous():
+            raise NativeError("reset must be the step's contiguous (n_envs,) bool output")
+        a.reset, a.step = reset.data_ptr(), step
+        rc = self._lib_record(C.byref(a), self._stream_of(self._dev_index))
+        if rc:
+            check(lib(), rc)

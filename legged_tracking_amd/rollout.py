@@ -1000,12 +1000,31 @@ class Runner:
                         "mean_decoder_loss_student", "mean_adaptation_module_test_loss", "mean_decoder_test_loss",
                         "mean_decoder_test_loss_student")
                 wandb.log({"metrics": dict(zip(keys, losses))})
+            if self.runner_args.save_video_interval and self.log_wandb:
+                self.log_video(it)
             self.tot_timesteps += self.num_steps_per_env * self.env.num_envs
             self.tot_time += time.time() - start
             self.current_learning_iteration = it
             if it % self.runner_args.save_interval == 0:
                 self.save(self.checkpoint_dir())
         self.save(self.checkpoint_dir())
+
+    def log_video(self, it):
+        """log_video (ppo_cse/__init__.py:322-336): arm a recording every save_video_interval iterations and log
+        the episode once it is complete; with save_dir set the episode is also written to videos/{it:05d}.gif."""
+        if it - self.last_recording_it >= self.runner_args.save_video_interval:
+            self.env.start_recording()
+            self.last_recording_it = it
+        frames = self.env.get_complete_frames()
+        if len(frames) > 0:
+            self.env.pause_recording()
+            import wandb
+            frames_np = np.stack(frames).transpose(0, 3, 1, 2)
+            # no step=: this Runner's other wandb.log calls use wandb's own step counter
+            wandb.log({"train": {"video": wandb.Video(frames_np, fps=1 / self.env.dt, format="mp4")}})
+            if self.save_dir is not None:
+                from . import video
+                video.save_frames(frames, os.path.join(self.save_dir, "videos", f"{it:05d}.gif"), fps=1 / self.env.dt)
 
     def checkpoint_dir(self):
         """Where the reference's Runner writes checkpoints (ppo_cse/__init__.py:276-279):

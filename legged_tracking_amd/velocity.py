@@ -467,6 +467,8 @@ class VelocityTrackingEasyEnv(EnvBase):
         events = self.kernel_events.popleft() if self.kernel_events else None
         args.ev_begin, args.ev_end = events if events is not None else (None, None)
         self._sim.step(args)
+        if self._rec is not None:  # a recording is armed: its launch follows the step's launches on the same stream
+            self._record_step(self._reset[s])
         self._last_hist = hist
         self._rng_step += 1
         self._slot = (s + 1) % OUT_RING
