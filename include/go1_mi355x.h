@@ -17,6 +17,8 @@
  *                         (_get_env_origins :1808-1847)
  *   go1_tunnel_tiles() <- Terrain(cfg) tile generation (go1_gym/utils/tunnel.py:51-217,
  *                         tunnel_fn.py:99-163), seeded numpy stream reproduced on the device
+ *   go1_tunnel_generate() <- the same for terrain_type single_path, narrow_path (tunnel_fn.py:44-97)
+ *                         and random_pyramid (:546-581, tunnel.py:164-183)
  *
  * All device pointers are owned by the caller (PyTorch tensors); the library
  * never allocates or frees them.  Every call is asynchronous on the caller's
@@ -121,7 +123,7 @@ typedef struct go1_config {
   int32_t decimation;          /* 4 (go1_crawling.py:37) */
   int32_t n_internal;          /* physics sub-steps per sim step (native integrator) */
   int32_t rand_interval;       /* ceil(rand_interval_s / dt) (:1873) */
-  int32_t hf_nx, hf_ny;        /* tile pixels: 80 x 40 for single_path */
+  int32_t hf_nx, hf_ny;        /* tile pixels: int(terrain_length / hs) x int(terrain_width / hs), 80 x 40 for the README tunnel */
   int32_t env_id_offset;       /* global id of local env 0 (rank * n_envs): keys the Philox streams */
   int32_t n_terms;             /* reward terms with a nonzero scale, <= GO1_MAX_TERMS */
   int32_t term_ids[GO1_MAX_TERMS]; /* go1_term of reward slot k, in Cfg.reward_scales order */
@@ -343,6 +345,36 @@ typedef struct go1_tunnel_params {
 } go1_tunnel_params;
 int go1_tunnel_tiles(const go1_tunnel_params* p, const int32_t* extents, double* records, float* tiles,
                      void* stream);
+/* The same generator for every tunnel producer on this path (Cfg.terrain.terrain_type):
+ *   GO1_TUNNEL_SINGLE_PATH    TerrainFunctions.single_path (tunnel_fn.py:99-163), what go1_tunnel_tiles builds;
+ *   GO1_TUNNEL_NARROW_PATH    TerrainFunctions.narrow_path (:44-97): single_path's draws, one axis-aligned box per
+ *                             wedge written with Python slice semantics, later boxes over earlier ones;
+ *   GO1_TUNNEL_RANDOM_PYRAMID TerrainFunctions.random_pyramid (:546-581) with the parameters Terrain.make_terrain
+ *                             passes (tunnel.py:164-183): (num_x + 2 - d_num) x (num_y + 2 - d_num) pyramids per
+ *                             layer from Cfg.terrain.top / .bottom, d_num = 2 / 1 / 0 for the sub-terrain's
+ *                             difficulty draw < 0.25 / < 0.625 / otherwise.
+ * extents and tiles as for go1_tunnel_tiles; records: n_sub * GO1_TUNNEL_SPEC_REC doubles of device scratch.
+ * GO1_E_ARG (with go1_last_error) for a kind it does not know and, for GO1_TUNNEL_RANDOM_PYRAMID, for a layer
+ * with more than GO1_TUNNEL_MAX_WEDGES pyramids ((num_x + 2) (num_y + 2) at d_num = 0) or with num_x or num_y
+ * below 1 (num + 2 - d_num would not be positive at d_num = 2).  go1_tunnel_params.p_flat / p_double are not
+ * read for GO1_TUNNEL_RANDOM_PYRAMID, top / bottom not for the other two. */
+#define GO1_TUNNEL_SINGLE_PATH 0
+#define GO1_TUNNEL_NARROW_PATH 1
+#define GO1_TUNNEL_RANDOM_PYRAMID 2
+#define GO1_TUNNEL_MAX_WEDGES 64 /* pyramid_num up to 6 x 6 */
+#define GO1_TUNNEL_SPEC_REC (8 + 2 * 5 * GO1_TUNNEL_MAX_WEDGES)
+typedef struct go1_pyramid_params { /* Cfg.terrain.top / .bottom (config.py:113-132) */
+  int32_t num_x, num_y;             /* pyramid_num_x, pyramid_num_y */
+  double var_x, var_y, length_min, length_max, height_min, height_max;
+} go1_pyramid_params;
+typedef struct go1_tunnel_spec {
+  go1_tunnel_params base;
+  int32_t kind; /* GO1_TUNNEL_* */
+  int32_t pad;
+  go1_pyramid_params top, bottom;
+} go1_tunnel_spec;
+int go1_tunnel_generate(const go1_tunnel_spec* spec, const int32_t* extents, double* records, float* tiles,
+                        void* stream);
 int go1_step(go1_handle* h, const go1_step_args* args, void* stream);
 /* Kernel variant.  go1_create selects a step kernel specialised for the README configuration
  * (scripts/train.py's README command: the integer flags of legged_tracking_amd/csrc/go1_spec.h

@@ -131,6 +131,23 @@ class Go1TunnelParams(C.Structure):
                 ("p_double", C.c_double)]
 
 
+# go1_tunnel_generate (the same generator for every tunnel producer; kind = terrain.KINDS index)
+GO1_TUNNEL_SINGLE_PATH, GO1_TUNNEL_NARROW_PATH, GO1_TUNNEL_RANDOM_PYRAMID = 0, 1, 2
+GO1_TUNNEL_MAX_WEDGES = 64
+GO1_TUNNEL_SPEC_REC = 8 + 2 * 5 * GO1_TUNNEL_MAX_WEDGES
+
+
+class Go1PyramidParams(C.Structure):
+    _fields_ = [("num_x", I32), ("num_y", I32), ("var_x", C.c_double), ("var_y", C.c_double),
+                ("length_min", C.c_double), ("length_max", C.c_double), ("height_min", C.c_double),
+                ("height_max", C.c_double)]
+
+
+class Go1TunnelSpec(C.Structure):
+    _fields_ = [("base", Go1TunnelParams), ("kind", I32), ("pad", I32), ("top", Go1PyramidParams),
+                ("bottom", Go1PyramidParams)]
+
+
 class Go1StepArgs(C.Structure):
     _fields_ = [
         ("actions", P), ("gravity_vec", F * 3), ("sim_gravity", F * 3), ("reward_scales", F * GO1_MAX_TERMS),

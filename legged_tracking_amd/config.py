@@ -137,6 +137,27 @@ def make_cfg():
             measure_front_half = True
             terminate_end_of_trajectory = False
 
+            # settings for random_pyramid (config.py:113-132)
+            class top(PrefixProto, cli=False):
+                pyramid_num_x = 3
+                pyramid_num_y = 5
+                pyramid_var_x = 0.5
+                pyramid_var_y = 0.3
+                pyramid_length_min = 0.2
+                pyramid_length_max = 0.4
+                pyramid_height_min = 0.2
+                pyramid_height_max = 0.4
+
+            class bottom(PrefixProto, cli=False):
+                pyramid_num_x = 3
+                pyramid_num_y = 5
+                pyramid_var_x = 0.5
+                pyramid_var_y = 0.3
+                pyramid_length_min = 0.2
+                pyramid_length_max = 0.4
+                pyramid_height_min = 0.2
+                pyramid_height_max = 0.4
+
         class commands(PrefixProto, cli=False):
             switch_upon_reach = True
             switch_interval = 0.5
@@ -631,17 +652,24 @@ def readme_config(n_envs=4096, terrain="single_path", rows=32, cols=32, camera_z
     --penalty_scaler 1.0 --strategy e2e --terminal_body_height 0.0), with
     num_envs / terrain grid overridable (train.py:128-130 hard-codes 1024/32/32).
     `extra_argv` appends further train.py flags (variants)."""
-    if terrain not in ("plane", "single_path"):
-        raise ValueError(f"terrain {terrain!r}: only plane and single_path are on this path")
+    if terrain != "plane" and terrain not in TUNNEL_TYPES:
+        raise ValueError(f"terrain {terrain!r}: only plane, {', '.join(TUNNEL_TYPES)} are on this path")
     if camera_zero is None:
         camera_zero = terrain != "plane"  # plane + camera_zero crashes in the reference (:402)
-    argv = ["--terrain", terrain, "--measure_front_half", "--penalty_scaler", "1.0", "--strategy", "e2e",
+    # train.py's --terrain knows plane / single_path / multi_path only: narrow_path and random_pyramid take
+    # its single_path tunnel settings (geometry, ceiling, start_loc, p_flat, p_double, episode length) and
+    # replace the terrain_type afterwards
+    flag = terrain if terrain == "plane" else "single_path"
+    argv = ["--terrain", flag, "--measure_front_half", "--penalty_scaler", "1.0", "--strategy", "e2e",
             "--terminal_body_height", "0.0"]
     if camera_zero:
         argv.append("--camera_zero")
     if not domain_rand:
         argv.append("--no_domain_rand")
-    return train_config(argv + list(extra_argv), n_envs=n_envs, rows=rows, cols=cols)
+    C = train_config(argv + list(extra_argv), n_envs=n_envs, rows=rows, cols=cols)
+    if terrain != "plane":
+        C.terrain.terrain_type = terrain
+    return C
 
 
 # ------------------------------------------------------------------ derived values
@@ -836,6 +864,13 @@ def traj_draws(cfg):
     return 0
 
 
+# the tunnel producers of terrain.make_tunnel / go1_tunnel_generate.  Not on this path: "random" (Isaac Gym's
+# random_uniform_terrain), "multi_path" (absent from the reference's TerrainFunctions) and the "old terrains"
+# test_env .. test_env_7, which the reference itself cannot build (tunnel.py:185 passes cfg positionally to
+# functions declared (terrain, top=True): TypeError)
+TUNNEL_TYPES = ("single_path", "narrow_path", "random_pyramid")
+
+
 def unsupported(cfg):
     """[(path, value, allowed, reference line)] for every Cfg value the HIP step does not implement."""
     bad = []
@@ -846,8 +881,8 @@ def unsupported(cfg):
         if v not in allowed:
             bad.append((path, v, allowed, ref))
     mesh, ttype = _get(cfg, "terrain.mesh_type", "trimesh"), _get(cfg, "terrain.terrain_type", "")
-    if mesh != "plane" and ttype != "single_path":
-        bad.append(("terrain.terrain_type", ttype, ("single_path",), "tunnel_fn.py:99-163"))
+    if mesh != "plane" and ttype not in TUNNEL_TYPES:
+        bad.append(("terrain.terrain_type", ttype, TUNNEL_TYPES, "tunnel_fn.py:44-163, 546-581"))
     return bad
 
 

@@ -278,12 +278,16 @@ class LeggedRobot(EnvBase):
         self.reward_names = list(self.reward_scales)
         self.sum_keys = tuple(self.reward_names) + ("total", "total_pos", "total_neg")
         n, n_global = self.num_envs, self._n_global
-        self._abi_cfg = CF.build_abi_config(cfg, n_envs=n, physics=physics)
+        # the kernels index the tiles as (hf_nx, hf_ny): the Cfg's own tile geometry, not the README's 80 x 40
+        plane = cfg.terrain.mesh_type == "plane"
+        lay = None if plane else T.tunnel_layout(cfg.terrain)
+        self._abi_cfg = CF.build_abi_config(cfg, n_envs=n, physics=physics,
+                                            **({} if plane else {"hf_shape": (lay.tile_x, lay.tile_y)}))
         self._abi_cfg.env_id_offset = rank * n
         # terrain: the global grid is built identically on every rank (same seed), each
         # rank binds the slice of global env ids it owns (_get_env_origins :1808-1847)
-        # the tunnel tiles come from the GPU generator (go1_tunnel_tiles) with the native backend,
-        # bit-identical to the host restatement T.make_single_path that injected test backends use
+        # the tunnel tiles come from the GPU generator (go1_tunnel_generate) with the native backend,
+        # bit-identical to the host restatement T.make_tunnel that injected test backends use
         tiles_fn = None
         if backend is None:  # the HIP library (no CPU fallback); tests inject a factory
             from . import native

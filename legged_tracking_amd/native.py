@@ -58,6 +58,7 @@ _ARGTYPES = {
     "go1_specialize": [C.c_void_p, C.c_int],
     "go1_is_specialized": [C.c_void_p],
     "go1_tunnel_tiles": [C.POINTER(abi.Go1TunnelParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "go1_tunnel_generate": [C.POINTER(abi.Go1TunnelSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
 }
 
 
@@ -105,19 +106,36 @@ class NativeHandle:
             pass
 
 
+def _pyramid_params(c):
+    return abi.Go1PyramidParams(num_x=int(c.pyramid_num_x), num_y=int(c.pyramid_num_y),
+                                var_x=float(c.pyramid_var_x), var_y=float(c.pyramid_var_y),
+                                length_min=float(c.pyramid_length_min), length_max=float(c.pyramid_length_max),
+                                height_min=float(c.pyramid_height_min), height_max=float(c.pyramid_height_max))
+
+
 def tunnel_tiles(cfg_terrain, layout, seed, device):
-    """single_path tiles generated on the GPU (go1_tunnel_tiles): the tiles the reference's
+    """Tunnel tiles of cfg_terrain.terrain_type generated on the GPU: the tiles the reference's
     Terrain(cfg) builds after np.random.seed(seed), as a (rows, cols, 2, tile_x, tile_y) f32
-    tensor on `device` (tunnel.py:51-217, tunnel_fn.py:99-163)."""
+    tensor on `device` (tunnel.py:51-217; tunnel_fn.py:99-163 single_path, :44-97 narrow_path,
+    :546-581 random_pyramid).  single_path goes through go1_tunnel_tiles, the other two through
+    go1_tunnel_generate.  ValueError before any device work for what the generators reject."""
+    from . import terrain as T
     t = cfg_terrain
     rows, cols = int(t.num_rows), int(t.num_cols)
     if not 0 <= int(seed) < 2 ** 32:
         raise ValueError("seed must be in [0, 2**32) (numpy RandomState)")
+    if t.terrain_type not in T.KINDS:
+        raise ValueError(f"terrain_type {t.terrain_type!r}: the generator builds {', '.join(T.KINDS)}")
+    kind = T.KINDS.index(t.terrain_type)
+    pyramid = kind == abi.GO1_TUNNEL_RANDOM_PYRAMID
+    if pyramid:
+        T.check_pyramid_params(t)
     p = abi.Go1TunnelParams(num_rows=rows, num_cols=cols, tile_x=layout.tile_x, tile_y=layout.tile_y,
                             sub_x=layout.sub_shape[0], sub_y=layout.sub_shape[1], seed=int(seed),
                             horizontal_scale=float(t.horizontal_scale), vertical_scale=float(t.vertical_scale),
-                            ceiling_height=float(t.ceiling_height), p_flat=float(t.p_flat),
-                            p_double=float(t.p_double))
+                            ceiling_height=float(t.ceiling_height),
+                            # (the reference's default Cfg has neither: train.py sets them for single_path)
+                            p_flat=0.0 if pyramid else float(t.p_flat), p_double=0.0 if pyramid else float(t.p_double))
     ex = np.ascontiguousarray(layout.extents, np.int32)
     span = np.stack([ex[:, 1] - ex[:, 0], ex[:, 3] - ex[:, 2]], 1)
     bad = np.nonzero((span != np.array([layout.sub_shape[1], layout.sub_shape[0]])).any(1))[0]
@@ -126,11 +144,19 @@ def tunnel_tiles(cfg_terrain, layout, seed, device):
         raise ValueError(f"sub-terrain {k}: tunnel extent {tuple(span[k])} does not match the sub-terrain shape "
                          f"{(layout.sub_shape[1], layout.sub_shape[0])} (could not broadcast)")
     ext = torch.as_tensor(ex).to(device)
-    rec = torch.empty((rows * cols, abi.GO1_TUNNEL_REC), dtype=torch.float64, device=device)
+    rec_w = abi.GO1_TUNNEL_REC if kind == abi.GO1_TUNNEL_SINGLE_PATH else abi.GO1_TUNNEL_SPEC_REC
+    rec = torch.empty((rows * cols, rec_w), dtype=torch.float64, device=device)
     tiles = torch.empty((rows, cols, 2, layout.tile_x, layout.tile_y), dtype=torch.float32, device=device)
     with torch.cuda.device(device):
-        check(lib(), lib().go1_tunnel_tiles(C.byref(p), ext.data_ptr(), rec.data_ptr(), tiles.data_ptr(),
-                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if kind == abi.GO1_TUNNEL_SINGLE_PATH:
+            rc = lib().go1_tunnel_tiles(C.byref(p), ext.data_ptr(), rec.data_ptr(), tiles.data_ptr(), stream)
+        else:
+            spec = abi.Go1TunnelSpec(base=p, kind=kind)
+            if pyramid:
+                spec.top, spec.bottom = _pyramid_params(t.top), _pyramid_params(t.bottom)
+            rc = lib().go1_tunnel_generate(C.byref(spec), ext.data_ptr(), rec.data_ptr(), tiles.data_ptr(), stream)
+        check(lib(), rc)
     torch.cuda.current_stream(device).synchronize()  # ext / rec are freed on return
     return tiles
 
@@ -202,6 +228,10 @@ class Go1Native(NativeHandle):
              torch.as_tensor(np.ascontiguousarray(env_tile, np.int32)).to(d),
              torch.as_tensor(np.ascontiguousarray(env_terrain_origin, np.float32)).to(d),
              torch.as_tensor(np.ascontiguousarray(env_origins, np.float32)).to(d)]
+        if self.cfg.terrain_kind == 1 and tuple(t[0].shape[1:]) != (2, self.cfg.hf_nx, self.cfg.hf_ny):
+            # the kernels take the tile shape from the config: another shape would be mis-indexed without any error
+            raise NativeError(f"terrain tiles are {tuple(t[0].shape)}, the handle's config indexes them as "
+                              f"(n_tiles, 2, {self.cfg.hf_nx}, {self.cfg.hf_ny}) (go1_config.hf_nx / hf_ny)")
         self._terrain_keep = t
         s = abi.Go1Terrain(tiles=t[0].data_ptr(), env_tile=t[1].data_ptr(), env_terrain_origin=t[2].data_ptr(),
                            env_origins=t[3].data_ptr(), n_tiles=int(t[0].shape[0]))

@@ -1,9 +1,11 @@
 """python -m legged_tracking_amd.play LOGDIR --out DIR [--steps 500] [--envs 16] [--width 640] [--height 480]
+                                      [--terrain single_path|narrow_path|random_pyramid]
 
 What the reference's scripts/eval.py:68-173 does, without the plots: load a Runner checkpoint (LOGDIR/ac_weights.pt
 or LOGDIR/checkpoints/ac_weights.pt; the Cfg of LOGDIR/parameters.pkl when it is there), build a 4 x 4 tunnel grid
 with the domain randomisation switched off and record_all_envs on, run the policy and write one GIF per env
-(env_{i}.gif; .npy without PIL) from render_all_envs()."""
+(env_{i}.gif; .npy without PIL) from render_all_envs().  The tunnel is the checkpoint's own terrain_type
+(single_path without a parameters.pkl) unless --terrain names another producer."""
 import argparse
 import os
 import pickle
@@ -28,9 +30,19 @@ def _find(logdir, name):
     return None
 
 
-def load_cfg(logdir, n_envs, width, height):
+def _apply(section, values):
+    """Saved {key: value} onto a Cfg section; a nested dict goes into the sub-section of that name
+    (terrain.top / terrain.bottom, sim.physx)."""
+    for k, v in values.items():
+        if isinstance(v, dict) and isinstance(getattr(section, k, None), type):
+            _apply(getattr(section, k), v)
+        else:
+            setattr(section, k, v)
+
+
+def load_cfg(logdir, n_envs, width, height, terrain=None):
     """readme_config on a 4 x 4 grid, overridden by parameters.pkl ({section: {key: value}}) and then by
-    eval.py's play settings (:82-101)."""
+    eval.py's play settings (:82-101).  `terrain` replaces the terrain_type (the checkpoint's, or single_path)."""
     # a 4 x 4 grid (:87-88); fewer than 16 envs get the largest square grid that their number fills evenly
     g = max(k for k in (1, 2, 3, 4) if n_envs % (k * k) == 0)
     cfg = CF.readme_config(n_envs=n_envs, terrain="single_path", rows=g, cols=g)
@@ -40,8 +52,9 @@ def load_cfg(logdir, n_envs, width, height):
             saved = pickle.load(f)
         for section, values in saved.items():
             if hasattr(cfg, section) and isinstance(values, dict):
-                for k, v in values.items():
-                    setattr(getattr(cfg, section), k, v)
+                _apply(getattr(cfg, section), values)
+    if terrain is not None:
+        cfg.terrain.terrain_type = terrain
     e = cfg.env
     e.recording_width_px, e.recording_height_px = int(width), int(height)
     e.num_envs, e.look_from_back, e.record_all_envs = int(n_envs), True, True
@@ -51,14 +64,14 @@ def load_cfg(logdir, n_envs, width, height):
     return cfg
 
 
-def play(logdir, out, steps=500, envs=16, width=640, height=480, device="cuda:0", seed=11):
+def play(logdir, out, steps=500, envs=16, width=640, height=480, device="cuda:0", seed=11, terrain=None):
     """Returns the files written, one per env."""
     weights = _find(logdir, "ac_weights.pt")
     if weights is None:
         raise FileNotFoundError(f"no ac_weights.pt under {logdir}")
     envs = int(envs)
     n_built = -(-envs // 16) * 16  # the HIP step takes multiples of 16 envs; the first `envs` are written
-    cfg = load_cfg(logdir, n_built, width, height)
+    cfg = load_cfg(logdir, n_built, width, height, terrain)
     env = HistoryWrapper(TrajectoryTrackingEnv(sim_device=device, headless=True, cfg=cfg, seed=seed))
     ac = ActorCritic(env.num_obs, env.num_privileged_obs, env.num_obs_history, env.num_actions).to(env.device)
     ac.load_state_dict(torch.load(weights, map_location=env.device, weights_only=True))
@@ -83,8 +96,10 @@ def main(argv=None):
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--terrain", default=None, choices=list(CF.TUNNEL_TYPES),
+                    help="tunnel producer (default: the checkpoint's terrain_type, single_path without one)")
     a = ap.parse_args(argv)
-    for p in play(a.logdir, a.out, a.steps, a.envs, a.width, a.height, a.device):
+    for p in play(a.logdir, a.out, a.steps, a.envs, a.width, a.height, a.device, terrain=a.terrain):
         print(p)
 
 
