@@ -32,6 +32,7 @@
 extern "C" {
 #endif
 
+#define GO1_PPO_ABI_VERSION 1
 #define GO1_PPO_OK 0
 #define GO1_PPO_E_ARG -1
 #define GO1_PPO_E_HIP -2
@@ -86,6 +87,10 @@ typedef struct go1_ppo_bufs {
   void* work;                    /* go1_ppo_workspace_bytes() bytes, 256-byte aligned, zeroed once before first use */
 } go1_ppo_bufs;
 
+int go1_ppo_abi_version(void);
+/* sizeof(go1_ppo_dims), sizeof(go1_ppo_hyper), sizeof(go1_ppo_bufs): lets a foreign binding verify its struct
+ * mirrors (go1_ppo_hyper is one float per field). */
+void go1_ppo_abi_sizes(int64_t out[3]);
 const char* go1_ppo_last_error(void);
 /* number of parameters (floats), and of the adaptation module's (the leading slice) */
 int go1_ppo_param_count(const go1_ppo_dims* d, int64_t* total, int64_t* adaptation);

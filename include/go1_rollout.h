@@ -23,6 +23,7 @@
 extern "C" {
 #endif
 
+#define GO1_ROLLOUT_ABI_VERSION 1
 #define GO1_OK_RT 0
 #define GO1_RT_E_ARG -1
 #define GO1_RT_E_HIP -2
@@ -97,6 +98,10 @@ typedef struct go1_policy_args {
   int64_t hist_ld;             /* row stride of obs_history in floats (0: hist_dim; >= hist_dim) */
 } go1_policy_args;
 
+int go1_rollout_abi_version(void);
+/* sizeof(go1_transition), sizeof(go1_policy_layer), sizeof(go1_policy_args): lets a foreign binding verify
+ * its struct mirrors. */
+void go1_rollout_abi_sizes(int64_t out[3]);
 const char* go1_rollout_last_error(void);
 int go1_policy_forward(const go1_policy_args* args, void* stream);
 int go1_record_transition(const go1_transition* tr, int32_t n_envs, float gamma, void* stream);

@@ -161,13 +161,6 @@ struct XwLaunch {
 
 enum { EPI_LIN = 0, EPI_ELU = 1, EPI_DELU = 2 };
 
-#ifndef PPO_XW_LB
-#define PPO_XW_LB 2
-#endif
-#ifndef PPO_XW_V
-#define PPO_XW_V 1  // 0: weight fragments loaded at the start of their K group; 1: one group ahead; 2: through LDS
-#endif
-
 #ifdef PPO_STAMPS  // diagnostic build only (tools/xw_stamps.py): s_memrealtime per workgroup at kernel start,
                    // after the first staged group, after the K loop and after the epilogue
 __device__ unsigned long long g_xw_stamps[8192][4];
@@ -180,7 +173,7 @@ __device__ unsigned long long g_xw_stamps[8192][4];
 #endif
 
 template <int EPI>
-__global__ __launch_bounds__(256, PPO_XW_LB) void xw_kernel(XwLaunch L) {
+__global__ __launch_bounds__(256, 2) void xw_kernel(XwLaunch L) {
   XW_STAMP(0);
   __shared__ h8_t sA[2][2][4][TB];  // [buffer][plane][q][row]: 32 KiB
   __shared__ float sRed[2][64];
@@ -261,34 +254,21 @@ __global__ __launch_bounds__(256, PPO_XW_LB) void xw_kernel(XwLaunch L) {
     }
   };
   load(0);
-#if PPO_XW_V == 1
   // weight fragments and the A tile of the next group in flight across this group's MFMAs: every load is
   // unconditional (the last group re-loads itself), the LDS store of the staged group follows the MFMAs
   h8_t wh0[4], wl0[4], wh1[4], wl1[4];
   loadw(0, wh0, wl0);
-#endif
   // the max |x| records (one dependent round trip) after the first group's loads are in flight
   eA = scale_exp(P.amax2 ? max(*P.amax, *P.amax2) : *P.amax);
   eW = *P.wexp;
   sa = pow2f(eA);
   store(0);
-#if PPO_XW_V == 1
   __syncthreads();
   auto body = [&](int g, int cur, h8_t (&wh)[4], h8_t (&wl)[4], h8_t (&nwh)[4], h8_t (&nwl)[4]) {
     const int gn = min(g + 1, G - 1);
-#ifndef PPO_XW_NOW  // timing experiments only: PPO_XW_NOW / NOA / NOMMA drop the weight loads / A loads / MFMAs
     loadw(gn, nwh, nwl);
-#else
-    (void)nwh; (void)nwl;
-#endif
-#ifndef PPO_XW_NOA
     load(gn);
-#endif
-#ifndef PPO_XW_NOMMA
     mma(cur, wh, wl);
-#else
-    if (g < 0) mma(cur, wh, wl);
-#endif
     store(cur ^ 1);
     __syncthreads();
   };
@@ -298,53 +278,6 @@ __global__ __launch_bounds__(256, PPO_XW_LB) void xw_kernel(XwLaunch L) {
     if (g + 1 < G) body(g + 1, 1, wh1, wl1, wh0, wl0);
   }
   XW_STAMP(2);
-#elif PPO_XW_V == 2
-  // weight tile through LDS: each thread stages 4 x 16 bytes of the next group's 16 KiB image with the A tile
-  __shared__ h8_t sW[2][2][4][TB];  // [buffer][plane][q][n]
-  const h8_t* wsrc = P.w + nt * TB + (tid & 31) + (size_t)(tid >> 5) * npad;  // chunk (plane, q) = tid >> 5
-  h8_t wst[4];
-  auto loadw2 = [&](int g) {
-    const h8_t* p = wsrc + (size_t)g * 8 * npad;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) wst[i] = p[32 * i];
-  };
-  auto storew2 = [&](int buf) {
-    h8_t* d = &sW[buf][0][0][0] + (size_t)(tid >> 5) * TB + (tid & 31);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) d[32 * i] = wst[i];
-  };
-  loadw2(0);
-  storew2(0);
-  __syncthreads();
-  for (int g = 0; g < G; ++g) {
-    const int cur = g & 1;
-    const int gn = min(g + 1, G - 1);  // unconditional: the last group re-loads itself into the idle buffer
-    loadw2(gn);
-    load(gn);
-    h8_t wh[4], wl[4];
-#pragma unroll
-    for (int tn = 0; tn < 4; ++tn) {
-      wh[tn] = sW[cur][0][q][wn * 64 + tn * 16 + c];
-      wl[tn] = sW[cur][1][q][wn * 64 + tn * 16 + c];
-    }
-    mma(cur, wh, wl);
-    store(cur ^ 1);
-    storew2(cur ^ 1);
-    __syncthreads();
-  }
-#else
-  __syncthreads();
-  for (int g = 0; g < G; ++g) {
-    const int cur = g & 1;
-    h8_t wh[4], wl[4];
-    loadw(g, wh, wl);
-    const bool more = g + 1 < G;
-    if (more) load(g + 1);
-    mma(cur, wh, wl);
-    if (more) store(cur ^ 1);
-    __syncthreads();
-  }
-#endif
   // epilogue.  The D form's ELU' operand: the next column block's rows are requested while this one is
   // finished (clamped rows, unconditional: a load under the row test would be waited for at once); rows past
   // M only skip their store.
@@ -386,9 +319,6 @@ __global__ __launch_bounds__(256, PPO_XW_LB) void xw_kernel(XwLaunch L) {
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) amax = max(amax, in ? absbits(v[i]) : 0u);
-#ifdef PPO_XW_NOSTORE  // timing experiment: no C stores
-      if (v[0] != v[0] && v[1] == 12345.0f)
-#endif
       if (in) *reinterpret_cast<f4_t*>(P.c + (size_t)m * P.ldc + n) = v;
     }
   }
@@ -1952,6 +1882,14 @@ int step_phase(const Ctx& C, int phase) {
 extern "C" {
 
 const char* go1_ppo_last_error(void) { return g_err.c_str(); }
+
+int go1_ppo_abi_version(void) { return GO1_PPO_ABI_VERSION; }
+
+void go1_ppo_abi_sizes(int64_t out[3]) {
+  out[0] = sizeof(go1_ppo_dims);
+  out[1] = sizeof(go1_ppo_hyper);
+  out[2] = sizeof(go1_ppo_bufs);
+}
 
 int go1_ppo_param_count(const go1_ppo_dims* d, int64_t* total, int64_t* adaptation) {
   Lay L;

@@ -243,9 +243,6 @@ __global__ __launch_bounds__(256) void record_flat_kernel(RecPlan P, go1_transit
 // nets).  Activations live in LDS already split, as [k/8][env][8] halves (hi plane, then lo plane): a
 // B fragment (k = 32 g + 8 q + r, env c) is one 16-byte read per plane, and a layer's output tile
 // (rows 4 q + r of env c) one 8-byte write.
-#ifndef GO1_POLICY_SCHED
-#define GO1_POLICY_SCHED 1
-#endif
 constexpr int PIN = 288;  // 261 / 263 inputs padded to a multiple of 32
 constexpr int PW = 16;    // waves per workgroup (four per SIMD)
 
@@ -331,30 +328,12 @@ __device__ __forceinline__ void policy_load(const PolicyLayer* L, int G, int g, 
 #pragma unroll
     for (int i = 0; i < NT; ++i)
       w[l][i] = reinterpret_cast<const f8_t*>(L[l].w)[((size_t)(tile0 + i * tstride) * G + g) * 64 + lane];
-#if GO1_POLICY_SCHED
   // keep the prefetch where it is written: otherwise the scheduler sinks the loads next to
   // their MFMAs and the waits become vmcnt(1), exposing the L2 latency every group
   __builtin_amdgcn_sched_barrier(0);
-#endif
 }
 
-template <int NT, int NL>
-__device__ __forceinline__ void policy_group(const f8_t (&w)[NL][NT], const ActV* src, int g, int q, int c,
-                                             f4_t (&acc)[NL][NT]) {
-#pragma unroll
-  for (int l = 0; l < NL; ++l) {
-    const h8_t xh = src[l].hi[(4 * g + q) * 16 + c], xl = src[l].lo[(4 * g + q) * 16 + c];
-#pragma unroll
-    for (int i = 0; i < NT; ++i) acc[l][i] = mfma3(w[l][i], xh, xl, acc[l][i]);
-  }
-}
-
-// NT output tiles (tile0 + i * tstride) of NL layers at the same depth (the actor and the critic
-// advance together) for the 16 envs: acc = b + W x, ELU (act), store split to dst.  The G K groups
-// are unrolled and the weight fragments run D groups ahead of the MFMAs: with three 8-cycle f16
-// MFMAs per fragment the layers are bound by the L2 -> CU weight stream, which needs ~12
-// 16-byte loads in flight per lane (64 B/clk/CU x the L2 latency, 16 waves).
-// the first D weight groups of a policy_tiles phase, issued early: they depend on nothing the
+// the first D weight groups of a policy_tiles_e phase, issued early: they depend on nothing the
 // workgroup computes, so the adaptation module's can be in flight while the inputs are staged
 template <int NT, int NL, int G, int D>
 __device__ __forceinline__ void policy_prefetch(const PolicyLayer* L, int tile0, int tstride, int lane,
@@ -363,18 +342,40 @@ __device__ __forceinline__ void policy_prefetch(const PolicyLayer* L, int tile0,
   for (int g = 0; g < D && g < G; ++g) policy_load<NT, NL>(L, G, g, tile0, tstride, lane, w[g]);
 }
 
-template <int NT, int NL, int G, int D, bool PREFETCHED = false>
-__device__ __forceinline__ void policy_tiles(const PolicyLayer* L, const ActV* src, int tile0, int tstride,
-                                             const ActV* dst, bool act, int lane, int* ovf,
-                                             f8_t (*pre)[NL][NT] = nullptr) {
+// NT output tiles (tile0 + i * tstride) of NL layers at the same depth (the actor and the critic
+// advance together) for ET env tiles of 16 envs that share every weight fragment (src / dst [et][l]):
+// acc = b + W x, ELU (act), store split to dst.  The G K groups are unrolled and the weight fragments
+// run D groups ahead of the MFMAs: with three 8-cycle f16 MFMAs per fragment the layers are bound by
+// the L2 -> CU weight stream, which needs ~12 16-byte loads in flight per lane (64 B/clk/CU x the L2
+// latency, 16 waves).
+template <int NT, int NL, int ET>
+__device__ __forceinline__ void policy_group_e(const f8_t (&w)[NL][NT], const ActV (*src)[NL], int g, int q, int c,
+                                               f4_t (&acc)[ET][NL][NT]) {
+#pragma unroll
+  for (int l = 0; l < NL; ++l)
+#pragma unroll
+    for (int et = 0; et < ET; ++et) {
+      const h8_t xh = src[et][l].hi[(4 * g + q) * 16 + c], xl = src[et][l].lo[(4 * g + q) * 16 + c];
+#pragma unroll
+      for (int i = 0; i < NT; ++i) acc[et][l][i] = mfma3(w[l][i], xh, xl, acc[et][l][i]);
+    }
+}
+
+template <int NT, int NL, int ET, int G, int D, bool PREFETCHED = false>
+__device__ __forceinline__ void policy_tiles_e(const PolicyLayer* L, const ActV (*src)[NL], int tile0, int tstride,
+                                               const ActV (*dst)[NL], bool act, int lane, int* ovf,
+                                               f8_t (*pre)[NL][NT] = nullptr) {
   const int q = lane >> 4, c = lane & 15;
-  f4_t acc[NL][NT];
+  f4_t acc[ET][NL][NT];
   f8_t w[D][NL][NT];
 #pragma unroll
   for (int l = 0; l < NL; ++l)
 #pragma unroll
-    for (int i = 0; i < NT; ++i)
-      acc[l][i] = *reinterpret_cast<const f4_t*>(L[l].b + 16 * (tile0 + i * tstride) + 4 * q);
+    for (int i = 0; i < NT; ++i) {
+      const f4_t b = *reinterpret_cast<const f4_t*>(L[l].b + 16 * (tile0 + i * tstride) + 4 * q);
+#pragma unroll
+      for (int et = 0; et < ET; ++et) acc[et][l][i] = b;
+    }
   if constexpr (PREFETCHED) {
 #pragma unroll
     for (int g = 0; g < D; ++g)
@@ -387,36 +388,53 @@ __device__ __forceinline__ void policy_tiles(const PolicyLayer* L, const ActV* s
   }
 #pragma unroll
   for (int g = 0; g < G; ++g) {
-    policy_group<NT, NL>(w[g % D], src, g, q, c, acc);
+    policy_group_e<NT, NL, ET>(w[g % D], src, g, q, c, acc);
     if (g + D < G) policy_load<NT, NL>(L, G, g + D, tile0, tstride, lane, w[g % D]);
   }
 #pragma unroll
-  for (int l = 0; l < NL; ++l)
+  for (int et = 0; et < ET; ++et)
 #pragma unroll
-    for (int i = 0; i < NT; ++i) {
-      f4_t v = acc[l][i];
-      if (act) {
+    for (int l = 0; l < NL; ++l)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = elu(v[r]);
+      for (int i = 0; i < NT; ++i) {
+        f4_t v = acc[et][l][i];
+        if (act) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = elu(v[r]);
+        }
+        act_store4(dst[et][l], 4 * (tile0 + i * tstride) + q, c, v, ovf);
       }
-      act_store4(dst[l], 4 * (tile0 + i * tstride) + q, c, v, ovf);
-    }
 }
 
-// Partial product of one output tile over K groups [g0, g0 + NG), no bias: the K-split form of
-// the narrow layers (one wave walking all of K would run a serial MFMA chain behind one L2
-// round trip per group).  All NG weight fragments are loaded up front (one round trip).
+// the NG weight fragments of a tile_partial_e, loaded ahead (they depend on nothing the workgroup computes)
 template <int NG>
-__device__ __forceinline__ f4_t tile_partial(const PolicyLayer& L, int Gs, int tile, int g0, ActV src, int lane) {
-  const int q = lane >> 4, c = lane & 15;
-  f8_t w[NG];
+__device__ __forceinline__ void partial_load(const PolicyLayer& L, int Gs, int tile, int g0, int lane, f8_t (&w)[NG]) {
 #pragma unroll
   for (int i = 0; i < NG; ++i) w[i] = reinterpret_cast<const f8_t*>(L.w)[((size_t)tile * Gs + g0 + i) * 64 + lane];
-  f4_t acc = {0.0f, 0.0f, 0.0f, 0.0f};
+}
+
+// Partial products of one output tile over K groups [g0, g0 + NG) for ET env tiles, no bias: the
+// K-split form of the narrow layers (one wave walking all of K would run a serial MFMA chain behind
+// one L2 round trip per group).  All NG weight fragments are loaded up front (one round trip), or
+// taken from `pre`.
+template <int NG, int ET>
+__device__ __forceinline__ void tile_partial_e(const PolicyLayer& L, int Gs, int tile, int g0, const ActV* src, int lane,
+                                               f4_t (&acc)[ET], const f8_t* pre = nullptr) {
+  const int q = lane >> 4, c = lane & 15;
+  f8_t w[NG];
+  if (pre) {
+#pragma unroll
+    for (int i = 0; i < NG; ++i) w[i] = pre[i];
+  } else {
+    partial_load<NG>(L, Gs, tile, g0, lane, w);
+  }
+#pragma unroll
+  for (int et = 0; et < ET; ++et) acc[et] = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
   for (int i = 0; i < NG; ++i)
-    acc = mfma3(w[i], src.hi[(4 * (g0 + i) + q) * 16 + c], src.lo[(4 * (g0 + i) + q) * 16 + c], acc);
-  return acc;
+#pragma unroll
+    for (int et = 0; et < ET; ++et)
+      acc[et] = mfma3(w[i], src[et].hi[(4 * (g0 + i) + q) * 16 + c], src[et].lo[(4 * (g0 + i) + q) * 16 + c], acc[et]);
 }
 
 // ---------------------------------------------------------------- range guard: f32 fallback
@@ -512,11 +530,9 @@ __global__ __launch_bounds__(64 * PW) void policy_kernel(go1_policy_args P) {
   const ActV va = xa.v(), vc = xc.v();
   __shared__ int s_ovf;
   if (tid == 0) s_ovf = 0;
-#ifndef GO1_POLICY_NO_EARLY
   // the adaptation module's first weight groups are in flight while the inputs are staged
   f8_t w_ad[4][1][1];
   policy_prefetch<1, 1, PIN / 32, 4>(P.layers + 0, wave, PW, lane, w_ad);
-#endif
   for (int idx = tid; idx < 16 * PIN; idx += 64 * PW) {
     const int e = idx / PIN, k = idx - e * PIN;
     float v = 0.0f;
@@ -529,13 +545,11 @@ __global__ __launch_bounds__(64 * PW) void policy_kernel(go1_policy_args P) {
   __syncthreads();
   PSTAMP(1);
   const PolicyLayer* Ls = P.layers;
+  // the shared helpers take [env tile][layer] planes: one env tile here
   const ActV vh1[2] = {h1[0].v(), h1[1].v()}, vh2[2] = {h2[0].v(), h2[1].v()};
+  const ActV sa[1] = {va}, da[1] = {vh1[0]};
   // adaptation module (xa rows >= hist_dim are still zero)
-#ifndef GO1_POLICY_NO_EARLY
-  policy_tiles<1, 1, PIN / 32, 4, true>(Ls + 0, &va, wave, PW, &vh1[0], true, lane, &s_ovf, w_ad);  // 256
-#else
-  policy_tiles<1, 1, PIN / 32, 4>(Ls + 0, &va, wave, PW, &vh1[0], true, lane, &s_ovf);  // 256
-#endif
+  policy_tiles_e<1, 1, 1, PIN / 32, 4, true>(Ls + 0, &sa, wave, PW, &da, true, lane, &s_ovf, w_ad);  // 256
   __syncthreads();
   PSTAMP(2);
   // 256 -> 128: waves w and w + 8 take the two K halves of tile w & 7; the upper half's partial
@@ -543,17 +557,18 @@ __global__ __launch_bounds__(64 * PW) void policy_kernel(go1_policy_args P) {
   {
     float(*scr)[16][16] = reinterpret_cast<float(*)[16][16]>(&h2[1]);
     const int q = lane >> 4, c = lane & 15, t = wave & 7, half = wave >> 3;
-    f4_t acc = tile_partial<4>(Ls[1], 8, t, 4 * half, vh1[0], lane);
+    f4_t acc[1];
+    tile_partial_e<4, 1>(Ls[1], 8, t, 4 * half, &vh1[0], lane, acc);
     if (half) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) scr[t][4 * q + r][c] = acc[r];
+      for (int r = 0; r < 4; ++r) scr[t][4 * q + r][c] = acc[0][r];
     }
     __syncthreads();
     if (!half) {
       const f4_t b = *reinterpret_cast<const f4_t*>(Ls[1].b + 16 * t + 4 * q);
       f4_t v;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = elu((b[r] + acc[r]) + scr[t][4 * q + r][c]);
+      for (int r = 0; r < 4; ++r) v[r] = elu((b[r] + acc[0][r]) + scr[t][4 * q + r][c]);
       act_store4(vh2[0], 4 * t + q, c, v, &s_ovf);
     }
   }
@@ -564,9 +579,10 @@ __global__ __launch_bounds__(64 * PW) void policy_kernel(go1_policy_args P) {
     float(*scr)[16][16] = reinterpret_cast<float(*)[16][16]>(&h2[1]);
     const int q = lane >> 4, c = lane & 15;
     if (wave < 4) {
-      const f4_t acc = tile_partial<1>(Ls[2], 4, 0, wave, vh2[0], lane);
+      f4_t acc[1];
+      tile_partial_e<1, 1>(Ls[2], 4, 0, wave, &vh2[0], lane, acc);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) scr[wave][4 * q + r][c] = acc[r];
+      for (int r = 0; r < 4; ++r) scr[wave][4 * q + r][c] = acc[0][r];
     }
     __syncthreads();
     if (wave == 0 && q < 2) {
@@ -589,18 +605,18 @@ __global__ __launch_bounds__(64 * PW) void policy_kernel(go1_policy_args P) {
   const PolicyLayer LA1[2] = {Ls[3], Ls[7]}, LA2[2] = {Ls[4], Ls[8]};
   {
     const ActV s1[2] = {va, vc};
-    policy_tiles<2, 2, PIN / 32, 2>(LA1, s1, wave, PW, vh1, true, lane, &s_ovf);  // 512
+    policy_tiles_e<2, 2, 1, PIN / 32, 2>(LA1, &s1, wave, PW, &vh1, true, lane, &s_ovf);  // 512
   }
   __syncthreads();
   PSTAMP(5);
-  policy_tiles<1, 2, 512 / 32, 3>(LA2, vh1, wave, PW, vh2, true, lane, &s_ovf);  // 256
+  policy_tiles_e<1, 2, 1, 512 / 32, 3>(LA2, &vh1, wave, PW, &vh2, true, lane, &s_ovf);  // 256
   __syncthreads();
   PSTAMP(6);
   {  // 256 -> 128, one tile per wave: waves 0-7 the actor's, 8-15 the critic's
     const bool critic = wave >= 8;
     const PolicyLayer L3 = critic ? Ls[9] : Ls[5];
-    const ActV src = critic ? h2[1].v() : h2[0].v(), dst = critic ? h1[1].v() : h1[0].v();
-    policy_tiles<1, 1, 256 / 32, 4>(&L3, &src, wave & 7, 8, &dst, true, lane, &s_ovf);
+    const ActV src[1] = {critic ? h2[1].v() : h2[0].v()}, dst[1] = {critic ? h1[1].v() : h1[0].v()};
+    policy_tiles_e<1, 1, 1, 256 / 32, 4>(&L3, &src, wave & 7, 8, &dst, true, lane, &s_ovf);
   }
   __syncthreads();
   PSTAMP(7);
@@ -611,9 +627,11 @@ __global__ __launch_bounds__(64 * PW) void policy_kernel(go1_policy_args P) {
     const int q = lane >> 4, c = lane & 15;
     const bool critic = wave >= 8;
     if ((wave & 7) < 4) {
-      const f4_t part = tile_partial<1>(Ls[critic ? 10 : 6], 4, 0, wave & 7, critic ? h1[1].v() : h1[0].v(), lane);
+      f4_t part[1];
+      const ActV src = critic ? h1[1].v() : h1[0].v();
+      tile_partial_e<1, 1>(Ls[critic ? 10 : 6], 4, 0, wave & 7, &src, lane, part);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) scr[wave][4 * q + r][c] = part[r];
+      for (int r = 0; r < 4; ++r) scr[wave][4 * q + r][c] = part[0][r];
     }
   }
   __syncthreads();
@@ -684,100 +702,10 @@ __global__ __launch_bounds__(64 * PW) void policy_kernel(go1_policy_args P) {
 // workgroups run the adaptation module + actor (1.6 MB), the others the critic (1.2 MB), so a CU
 // streams at most 1.6 MB for twice the envs.  K order, tile split and partial-sum order are those
 // of policy_kernel, so the outputs are identical.
-// weight groups (32 K values) in flight per wave, the 512-wide first layers and the 256-wide second
-// (16-deep groups, round 2: (4, 8), (6, 12), (8, 12), (8, 16) all within 1 %)
-#ifndef GO1_SPLIT_D1
-#define GO1_SPLIT_D1 3
-#endif
-#ifndef GO1_SPLIT_D2
-#define GO1_SPLIT_D2 6
-#endif
-
-template <int NT, int NL, int ET>
-__device__ __forceinline__ void policy_group_e(const f8_t (&w)[NL][NT], const ActV (*src)[NL], int g, int q, int c,
-                                               f4_t (&acc)[ET][NL][NT]) {
-#pragma unroll
-  for (int l = 0; l < NL; ++l)
-#pragma unroll
-    for (int et = 0; et < ET; ++et) {
-      const h8_t xh = src[et][l].hi[(4 * g + q) * 16 + c], xl = src[et][l].lo[(4 * g + q) * 16 + c];
-#pragma unroll
-      for (int i = 0; i < NT; ++i) acc[et][l][i] = mfma3(w[l][i], xh, xl, acc[et][l][i]);
-    }
-}
-
-template <int NT, int NL, int ET, int G, int D, bool PREFETCHED = false>
-__device__ __forceinline__ void policy_tiles_e(const PolicyLayer* L, const ActV (*src)[NL], int tile0, int tstride,
-                                               const ActV (*dst)[NL], bool act, int lane, int* ovf,
-                                               f8_t (*pre)[NL][NT] = nullptr) {
-  const int q = lane >> 4, c = lane & 15;
-  f4_t acc[ET][NL][NT];
-  f8_t w[D][NL][NT];
-#pragma unroll
-  for (int l = 0; l < NL; ++l)
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-      const f4_t b = *reinterpret_cast<const f4_t*>(L[l].b + 16 * (tile0 + i * tstride) + 4 * q);
-#pragma unroll
-      for (int et = 0; et < ET; ++et) acc[et][l][i] = b;
-    }
-  if constexpr (PREFETCHED) {
-#pragma unroll
-    for (int g = 0; g < D; ++g)
-#pragma unroll
-      for (int l = 0; l < NL; ++l)
-#pragma unroll
-        for (int i = 0; i < NT; ++i) w[g][l][i] = pre[g][l][i];
-  } else {
-    policy_prefetch<NT, NL, G, D>(L, tile0, tstride, lane, w);
-  }
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    policy_group_e<NT, NL, ET>(w[g % D], src, g, q, c, acc);
-    if (g + D < G) policy_load<NT, NL>(L, G, g + D, tile0, tstride, lane, w[g % D]);
-  }
-#pragma unroll
-  for (int et = 0; et < ET; ++et)
-#pragma unroll
-    for (int l = 0; l < NL; ++l)
-#pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        f4_t v = acc[et][l][i];
-        if (act) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = elu(v[r]);
-        }
-        act_store4(dst[et][l], 4 * (tile0 + i * tstride) + q, c, v, ovf);
-      }
-}
-
-// tile_partial for ET env tiles sharing the weight fragments
-// the NG weight fragments of a tile_partial_e, loaded ahead (they depend on nothing the workgroup computes)
-template <int NG>
-__device__ __forceinline__ void partial_load(const PolicyLayer& L, int Gs, int tile, int g0, int lane, f8_t (&w)[NG]) {
-#pragma unroll
-  for (int i = 0; i < NG; ++i) w[i] = reinterpret_cast<const f8_t*>(L.w)[((size_t)tile * Gs + g0 + i) * 64 + lane];
-}
-
-template <int NG, int ET>
-__device__ __forceinline__ void tile_partial_e(const PolicyLayer& L, int Gs, int tile, int g0, const ActV* src, int lane,
-                                               f4_t (&acc)[ET], const f8_t* pre = nullptr) {
-  const int q = lane >> 4, c = lane & 15;
-  f8_t w[NG];
-  if (pre) {
-#pragma unroll
-    for (int i = 0; i < NG; ++i) w[i] = pre[i];
-  } else {
-    partial_load<NG>(L, Gs, tile, g0, lane, w);
-  }
-#pragma unroll
-  for (int et = 0; et < ET; ++et) acc[et] = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int i = 0; i < NG; ++i)
-#pragma unroll
-    for (int et = 0; et < ET; ++et)
-      acc[et] = mfma3(w[i], src[et].hi[(4 * (g0 + i) + q) * 16 + c], src[et].lo[(4 * (g0 + i) + q) * 16 + c], acc[et]);
-}
+// weight groups (32 K values) in flight per wave: the 512-wide first layers run two ahead (split_body's
+// load0 / load1 register sets), the 256-wide second layers SPLIT_D2 ahead (in 16-deep groups, (4, 8),
+// (6, 12), (8, 12) and (8, 16) for the two were all within 1 %)
+constexpr int SPLIT_D2 = 6;
 
 // LDS of policy_kernel_split: three env tiles of inputs and of 512-wide outputs.  Aliases (each used only
 // after a barrier that ends the previous use): the 256-wide L2 outputs live in the input planes (dead once
@@ -840,16 +768,11 @@ __device__ __forceinline__ void split_body(const go1_policy_args& P, SplitLds& S
   };
   // the first chunk's first two groups are requested before the inputs: they depend on nothing the workgroup
   // computes, so the weight stream starts under the input loads' latency instead of after the staging
-#ifndef GO1_POLICY_L1_EARLY
-#define GO1_POLICY_L1_EARLY 1
-#endif
-  if (GO1_POLICY_L1_EARLY) {
+  {
     const int gb0 = CRITIC ? min(CG, GL) : min(gl, min(CG, GL));
     if (0 < gb0) load0(0);
     if (1 < gb0) load1(1);
-#if GO1_POLICY_SCHED
     __builtin_amdgcn_sched_barrier(0);
-#endif
   }
   if (nch == 1) {
     constexpr int NI = (ET * 16 * PIN + 64 * PW - 1) / (64 * PW);
@@ -967,7 +890,7 @@ __device__ __forceinline__ void split_body(const go1_policy_args& P, SplitLds& S
           accL[et][1] = mfma3(l1, xh, xl, accL[et][1]);
         }
       };
-      if (ch > 0 || !GO1_POLICY_L1_EARLY) {  // the first chunk's were requested before the staging
+      if (ch > 0) {  // the first chunk's were requested before the staging
         if (g0 < gb) load0(g0);
         if (g0 + 1 < gb) load1(g0 + 1);
       }
@@ -1098,11 +1021,11 @@ __device__ __forceinline__ void split_body(const go1_policy_args& P, SplitLds& S
       for (int r = 0; r < 4; ++r) v[r] = elu(v[r]);
       act_store4(v1[et][0], 4 * (wave + i * PW) + q, c, v, s_ovf);
     }
-  f8_t pl2[GO1_SPLIT_D2][1][1];
-  policy_prefetch<1, 1, 512 / 32, GO1_SPLIT_D2>(LN + 1, wave, PW, lane, pl2);
+  f8_t pl2[SPLIT_D2][1][1];
+  policy_prefetch<1, 1, 512 / 32, SPLIT_D2>(LN + 1, wave, PW, lane, pl2);
   lds_barrier();
   PSTAMP(5);
-  policy_tiles_e<1, 1, ET, 512 / 32, GO1_SPLIT_D2, true>(LN + 1, v1, wave, PW, v2, true, lane, s_ovf, pl2);  // 256
+  policy_tiles_e<1, 1, ET, 512 / 32, SPLIT_D2, true>(LN + 1, v1, wave, PW, v2, true, lane, s_ovf, pl2);  // 256
   f8_t pl3[4][1][1];
   if (wave < 8) policy_prefetch<1, 1, 256 / 32, 4>(LN + 2, wave, 8, lane, pl3);
   lds_barrier();
@@ -1184,13 +1107,8 @@ __device__ __forceinline__ void split_body(const go1_policy_args& P, SplitLds& S
 // envs per workgroup: actor workgroups (adaptation module + actor, 1.6 MB of split weights) take SPLIT_ET_A
 // env tiles, critic workgroups (1.2 MB) SPLIT_ET_C, so the two kinds take about as long (4096 envs: actor
 // 65.8 k / critic 58.5 k cycles; with 3 + 3 tiles the actor workgroups grew to 84 k: 39 against 32.5 us)
-#ifndef GO1_SPLIT_ET_A
-#define GO1_SPLIT_ET_A 2
-#endif
-#ifndef GO1_SPLIT_ET_C
-#define GO1_SPLIT_ET_C 3
-#endif
-constexpr int SE_A = 16 * GO1_SPLIT_ET_A, SE_C = 16 * GO1_SPLIT_ET_C;
+constexpr int SPLIT_ET_A = 2, SPLIT_ET_C = 3;
+constexpr int SE_A = 16 * SPLIT_ET_A, SE_C = 16 * SPLIT_ET_C;
 
 __global__ __launch_bounds__(64 * PW) void policy_kernel_split(go1_policy_args P) {
   __shared__ SplitLds S;
@@ -1200,10 +1118,10 @@ __global__ __launch_bounds__(64 * PW) void policy_kernel_split(go1_policy_args P
   const int na = (P.n_envs + SE_A - 1) / SE_A;
   if ((int)blockIdx.x < na) {
     const int e0 = blockIdx.x * SE_A;
-    split_body<GO1_SPLIT_ET_A, false>(P, S, e0, min(SE_A, P.n_envs - e0), &s_ovf);
+    split_body<SPLIT_ET_A, false>(P, S, e0, min(SE_A, P.n_envs - e0), &s_ovf);
   } else {
     const int e0 = (blockIdx.x - na) * SE_C;
-    split_body<GO1_SPLIT_ET_C, true>(P, S, e0, min(SE_C, P.n_envs - e0), &s_ovf);
+    split_body<SPLIT_ET_C, true>(P, S, e0, min(SE_C, P.n_envs - e0), &s_ovf);
   }
 }
 
@@ -1265,6 +1183,14 @@ int go1_policy_stamps(void* host, size_t bytes) {
 #endif
 
 const char* go1_rollout_last_error(void) { return g_err.c_str(); }
+
+int go1_rollout_abi_version(void) { return GO1_ROLLOUT_ABI_VERSION; }
+
+void go1_rollout_abi_sizes(int64_t out[3]) {
+  out[0] = sizeof(go1_transition);
+  out[1] = sizeof(go1_policy_layer);
+  out[2] = sizeof(go1_policy_args);
+}
 
 int go1_record_transition(const go1_transition* tr, int32_t n_envs, float gamma, void* stream) {
   if (!tr || n_envs <= 0) return fail(GO1_RT_E_ARG, "go1_record_transition: bad argument");

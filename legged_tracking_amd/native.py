@@ -44,6 +44,19 @@ def check(l, rc):
         raise NativeError(l.last_error().decode())
 
 
+def raw_stream_of(device):
+    """A callable returning the hipStream_t (as an int) of torch's current stream on `device` (no index: the
+    device current now).  A partial of the C function, because the per-step paths call it."""
+    index = torch.device(device).index
+    return functools.partial(torch._C._cuda_getCurrentRawStream,
+                             index if index is not None else torch.cuda.current_device())
+
+
+def raw_stream(device="cuda"):
+    """The caller's current raw stream on `device`, for a call off the per-step path."""
+    return raw_stream_of(device)()
+
+
 _ARGTYPES = {
     "go1_create": [C.POINTER(abi.Go1Config), C.POINTER(C.c_void_p)],
     "go1_bind": [C.c_void_p, C.POINTER(abi.Go1State), C.POINTER(abi.Go1Plane)],
@@ -81,10 +94,7 @@ class NativeHandle:
         self.device = torch.device(device)
         self.h = C.c_void_p()
         self._lib, self._destroy = l, destroy
-        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        # hipStream_t (as an int) of torch's current stream on the handle's device; a partial of the C
-        # function, because the per-step path calls it
-        self._stream = functools.partial(torch._C._cuda_getCurrentRawStream, self._dev_index)
+        self._stream = raw_stream_of(self.device)
 
     def _check(self, rc):
         check(self._lib, rc)
@@ -148,7 +158,7 @@ def tunnel_tiles(cfg_terrain, layout, seed, device):
     rec = torch.empty((rows * cols, rec_w), dtype=torch.float64, device=device)
     tiles = torch.empty((rows, cols, 2, layout.tile_x, layout.tile_y), dtype=torch.float32, device=device)
     with torch.cuda.device(device):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        stream = raw_stream()
         if kind == abi.GO1_TUNNEL_SINGLE_PATH:
             rc = lib().go1_tunnel_tiles(C.byref(p), ext.data_ptr(), rec.data_ptr(), tiles.data_ptr(), stream)
         else:

@@ -19,62 +19,34 @@ import os
 
 import torch
 
+from . import learn_abi as LA, native
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GO1_PPO_LIB_OVERRIDE") or os.path.join(HERE, "_build", "libgo1_ppo.so")
 
-NAUX = 8
-HIDDEN_A = (256, 128)
-HIDDEN = (512, 256, 128)
-
+NAUX = LA.GO1_PPO_AUX
 # state_dict order of the supported ActorCritic, as the engine lays out its flat buffers (go1_ppo.h)
-PARAM_NAMES = [f"adaptation_module.{i}.{k}" for i in (0, 2, 4) for k in ("weight", "bias")] + \
-              [f"actor_body.{i}.{k}" for i in (0, 2, 4, 6) for k in ("weight", "bias")] + \
-              [f"critic_body.{i}.{k}" for i in (0, 2, 4, 6) for k in ("weight", "bias")] + ["std"]
-N_ADAPT_TENSORS = 6
+PARAM_NAMES = [f"{seq}.{i}.{k}" for seq, i in LA.POLICY_LINEARS for k in ("weight", "bias")] + ["std"]
+N_ADAPT_TENSORS = 2 * LA.N_ADAPT_LINEARS
 
-
-class _Dims(C.Structure):
-    _fields_ = [("hist", C.c_int32), ("priv", C.c_int32), ("actions", C.c_int32), ("mb", C.c_int32),
-                ("rows", C.c_int64)]
-
-
-class _Bufs(C.Structure):
-    _fields_ = [("obs_history", C.c_void_p), ("hist_ld", C.c_int64)] + \
-               [(k, C.c_void_p) for k in ("privileged_obs", "actions", "values", "advantages", "returns",
-                                          "actions_log_prob", "mu", "sigma", "idx", "params", "grads", "exp_avg",
-                                          "exp_avg_sq", "ad_exp_avg", "ad_exp_avg_sq", "steps", "lr", "hyper",
-                                          "losses", "work")]
-
-
-HYPER_FIELDS = ("clip_param", "value_loss_coef", "entropy_coef", "max_grad_norm", "desired_kl",
-                "use_clipped_value_loss", "selective", "beta1", "beta2", "eps", "world", "adaptation_lr")
-
-_LIB = []
+_lib = None
 
 
 def load_library(path=None):
-    """libgo1_ppo.so through ctypes; raises when the library or the GPU is missing (no CPU fallback).
-    `path`: another build of the same source (tools/ppo_gemm_bench.py compares variants)."""
-    if _LIB and path is None:
-        return _LIB[0]
-    path = path or LIB_PATH
-    if not os.path.exists(path):
-        raise RuntimeError(f"HIP PPO engine library missing: {path} (run __graft_entry__.build())")
-    lib = C.CDLL(path)
-    lib.go1_ppo_last_error.restype = C.c_char_p
-    P = C.POINTER
-    lib.go1_ppo_param_count.argtypes = [P(_Dims), P(C.c_int64), P(C.c_int64)]
-    lib.go1_ppo_workspace_bytes.argtypes = [P(_Dims), P(C.c_int64)]
-    lib.go1_ppo_pack.argtypes = [P(_Dims), P(_Bufs), C.c_void_p]
-    for f in ("go1_ppo_grad", "go1_ppo_step"):
-        getattr(lib, f).argtypes = [P(_Dims), P(_Bufs), C.c_int32, C.c_void_p]
-    lib.go1_ppo_test_linear.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
-                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
-    lib.go1_ppo_test_wgrad.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
-                                       C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
-    if path == LIB_PATH:
-        _LIB.append(lib)
-    return lib
+    """libgo1_ppo.so, loaded once; NativeError when it is missing or another ABI (no CPU fallback).
+    `path`: another build of the same source (tools/ppo_gemm_bench.py compares builds), loaded anew."""
+    global _lib
+    if path is None and _lib is not None:
+        return _lib
+    l = native.load_library(path or LIB_PATH, "go1_ppo_abi_version", LA.GO1_PPO_ABI_VERSION, "go1_ppo_last_error",
+                            LA.PPO_ARGTYPES)
+    sizes = (C.c_int64 * 3)()
+    l.go1_ppo_abi_sizes(sizes)
+    if sizes[1] != 4 * len(LA.HYPER_FIELDS):  # the hyper block is written as one float32 tensor
+        raise native.NativeError(f"go1_ppo_hyper is {sizes[1]} bytes, HYPER_FIELDS names {len(LA.HYPER_FIELDS)} floats")
+    if path is None:
+        _lib = l
+    return l
 
 
 def supported(ac):
@@ -86,16 +58,9 @@ def supported(ac):
         return False
     if sorted(names) != sorted(PARAM_NAMES) or len(a) != 5 or len(p) != 7 or len(c) != 7:
         return False
-    h, npv = ac.num_obs_history, ac.num_privileged_obs
-    na = p[6].out_features
-    want = {"adaptation_module.0": (HIDDEN_A[0], h), "adaptation_module.2": (HIDDEN_A[1], HIDDEN_A[0]),
-            "adaptation_module.4": (npv, HIDDEN_A[1]), "actor_body.0": (HIDDEN[0], h + npv),
-            "actor_body.2": (HIDDEN[1], HIDDEN[0]), "actor_body.4": (HIDDEN[2], HIDDEN[1]),
-            "actor_body.6": (na, HIDDEN[2]), "critic_body.0": (HIDDEN[0], h + npv),
-            "critic_body.2": (HIDDEN[1], HIDDEN[0]), "critic_body.4": (HIDDEN[2], HIDDEN[1]),
-            "critic_body.6": (1, HIDDEN[2])}
-    sd = dict(ac.named_parameters())
-    ok = all(tuple(sd[k + ".weight"].shape) == v for k, v in want.items())
+    lin = LA.policy_linears(ac)
+    npv, na = ac.num_privileged_obs, lin[6].out_features
+    ok = [tuple(m.weight.shape) for m in lin] == LA.policy_shapes(ac.num_obs_history, npv, na)
     acts = [m for seq in (a, p, c) for m in seq if not isinstance(m, torch.nn.Linear)]
     return (ok and 1 <= npv <= 8 and 1 <= na <= 16 and all(isinstance(m, torch.nn.ELU) and m.alpha == 1.0
                                                             for m in acts))
@@ -105,15 +70,16 @@ class PPOEngine:
     def __init__(self, alg):
         self.lib = load_library()
         if not torch.cuda.is_available():
-            raise RuntimeError("no GPU visible: the PPO update engine has no CPU fallback")
+            raise native.NativeError("no GPU visible: the PPO update engine has no CPU fallback")
         self.alg = alg
         ac = alg.actor_critic
         self.device = next(ac.parameters()).device
         self.hist, self.priv = ac.num_obs_history, ac.num_privileged_obs
         self.na = ac.actor_body[6].out_features
-        dims = _Dims(hist=self.hist, priv=self.priv, actions=self.na, mb=1, rows=1)
+        self._stream = native.raw_stream_of(self.device)
+        dims = LA.PPODims(hist=self.hist, priv=self.priv, actions=self.na, mb=1, rows=1)
         tot, ad = C.c_int64(), C.c_int64()
-        self._chk(self.lib.go1_ppo_param_count(C.byref(dims), C.byref(tot), C.byref(ad)))
+        native.check(self.lib, self.lib.go1_ppo_param_count(C.byref(dims), C.byref(tot), C.byref(ad)))
         self.n_total, self.n_adapt = tot.value, ad.value
         dev = self.device
         sd = dict(ac.named_parameters())
@@ -123,7 +89,7 @@ class PPOEngine:
             self.offsets[name] = off
             off += sd[name].numel()
         if off != self.n_total or self.offsets[PARAM_NAMES[N_ADAPT_TENSORS]] != self.n_adapt:
-            raise RuntimeError("PPO engine: parameter layout mismatch between the module and go1_ppo.h")
+            raise native.NativeError("PPO engine: parameter layout mismatch between the module and go1_ppo.h")
         # flat buffers; the module's parameters become views into `params`
         self.params = torch.empty(self.n_total, dtype=torch.float32, device=dev)
         for name in PARAM_NAMES:
@@ -137,27 +103,20 @@ class PPOEngine:
         self.ad_exp_avg_sq = torch.zeros_like(self.ad_exp_avg)
         self.steps = torch.zeros(2, dtype=torch.float32, device=dev)
         self.lr = torch.tensor([alg.learning_rate], dtype=torch.float64, device=dev)
-        self.hyper = torch.zeros(len(HYPER_FIELDS), dtype=torch.float32, device=dev)
+        self.hyper = torch.zeros(len(LA.HYPER_FIELDS), dtype=torch.float32, device=dev)
         self.losses = torch.zeros(4, dtype=torch.float64, device=dev)
         self._hyper_host = None
         self._lr_host = float(alg.learning_rate)
         self.work = None
         self.dims = None
-        self.bufs = _Bufs()
+        self.bufs = LA.PPOBufs()
         self.graphs = None
         self._graph_key = None
+        self.idx = self._draw = self._side = None  # mini-batch rows, the unused sample's arguments, capture stream
         self._import_optimizer_state()
         self._install_optimizer_views()
 
     # ------------------------------------------------------------------ helpers
-    def _chk(self, rc):
-        if rc != 0:
-            raise RuntimeError(self.lib.go1_ppo_last_error().decode())
-
-    @staticmethod
-    def _stream():
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def _param_list(self, adaptation_only=False):
         sd = dict(self.alg.actor_critic.named_parameters())
         names = PARAM_NAMES[:N_ADAPT_TENSORS] if adaptation_only else PARAM_NAMES
@@ -253,9 +212,9 @@ class PPOEngine:
 
     def _bind(self, st, mb):
         rows = st.num_envs * st.num_transitions_per_env
-        dims = _Dims(hist=self.hist, priv=self.priv, actions=self.na, mb=mb, rows=rows)
+        dims = LA.PPODims(hist=self.hist, priv=self.priv, actions=self.na, mb=mb, rows=rows)
         nb = C.c_int64()
-        self._chk(self.lib.go1_ppo_workspace_bytes(C.byref(dims), C.byref(nb)))
+        native.check(self.lib, self.lib.go1_ppo_workspace_bytes(C.byref(dims), C.byref(nb)))
         if self.work is None or self.work.numel() < nb.value:
             self.work = torch.zeros(nb.value + 256, dtype=torch.uint8, device=self.device)
             self.graphs = None
@@ -271,7 +230,7 @@ class PPOEngine:
         for k, t in zip(("privileged_obs", "actions", "values", "advantages", "returns", "actions_log_prob", "mu",
                          "sigma"), self._flat[1:]):
             setattr(b, k, t.data_ptr())
-        if getattr(self, "idx", None) is None or self.idx.numel() != mb:
+        if self.idx is None or self.idx.numel() != mb:
             self.idx = torch.zeros(mb, dtype=torch.int64, device=self.device)
             self.graphs = None
         b.idx = self.idx.data_ptr()
@@ -284,13 +243,13 @@ class PPOEngine:
 
     # ------------------------------------------------------------------ the C-ABI calls
     def pack(self):
-        self._chk(self.lib.go1_ppo_pack(C.byref(self.dims), C.byref(self.bufs), self._stream()))
+        native.check(self.lib, self.lib.go1_ppo_pack(C.byref(self.dims), C.byref(self.bufs), self._stream()))
 
     def grad(self, phase):
-        self._chk(self.lib.go1_ppo_grad(C.byref(self.dims), C.byref(self.bufs), phase, self._stream()))
+        native.check(self.lib, self.lib.go1_ppo_grad(C.byref(self.dims), C.byref(self.bufs), phase, self._stream()))
 
     def step(self, phase):
-        self._chk(self.lib.go1_ppo_step(C.byref(self.dims), C.byref(self.bufs), phase, self._stream()))
+        native.check(self.lib, self.lib.go1_ppo_step(C.byref(self.dims), C.byref(self.bufs), phase, self._stream()))
 
     def _allreduce(self, n):
         torch.distributed.all_reduce(self.grads[:NAUX + n])
@@ -326,7 +285,7 @@ class PPOEngine:
         self.pack()
         self.losses.zero_()
         indices = torch.randperm(num_mini_batches * mb, device=self.device)  # mini_batch_generator's draw
-        draw = getattr(self, "_draw", None)
+        draw = self._draw
         if draw is None or draw[0].shape != (mb, self.na):
             self._draw = draw = (torch.zeros(mb, self.na, device=self.device),
                                  torch.ones(mb, self.na, device=self.device))
@@ -354,7 +313,7 @@ class PPOEngine:
     def _capture(self, segs, gkey):
         """Capture the HIP segments (all-reduces stay eager callables between them), once the kernels are loaded."""
         torch.cuda.synchronize(self.device)
-        side = getattr(self, "_side", None)
+        side = self._side
         if side is None:
             side = self._side = torch.cuda.Stream(self.device)
         graphs = []

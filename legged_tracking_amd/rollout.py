@@ -29,6 +29,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.distributions import Normal
 
+from . import learn_abi as LA, native
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GO1_ROLLOUT_LIB_OVERRIDE") or os.path.join(HERE, "_build", "libgo1_rollout.so")
 
@@ -81,29 +83,16 @@ class RunnerArgs(_Args):
 
 
 # ----------------------------------------------------------------------------- native kernels
-class _Transition(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("obs", "privileged_obs", "obs_history", "actions", "mu", "sigma",
-                                          "actions_log_prob", "values", "rewards", "dones", "time_outs",
-                                          "st_obs", "st_privileged_obs", "st_obs_history", "st_actions", "st_mu",
-                                          "st_sigma", "st_actions_log_prob", "st_values", "st_rewards",
-                                          "st_dones")] + [
-        ("num_obs", C.c_int32), ("num_priv", C.c_int32), ("num_obs_history", C.c_int32), ("num_actions", C.c_int32),
-        ("time_outs_flag", C.c_void_p), ("time_outs_pending", C.c_void_p), ("time_outs_dst", C.c_void_p),
-        ("obs_history_ld", C.c_int64)]
+_lib = None
 
 
-class _PolicyLayer(C.Structure):
-    _fields_ = [("w", C.c_void_p), ("b", C.c_void_p), ("wf", C.c_void_p)]
-
-
-class _PolicyArgs(C.Structure):
-    _fields_ = [("obs_history", C.c_void_p), ("privileged_obs", C.c_void_p), ("action_mean", C.c_void_p),
-                ("value", C.c_void_p), ("latent", C.c_void_p), ("std", C.c_void_p), ("actions", C.c_void_p),
-                ("action_sigma", C.c_void_p), ("log_prob", C.c_void_p), ("rng_seed", C.c_uint64),
-                ("rng_step", C.c_uint64), ("env_id_offset", C.c_int32), ("n_envs", C.c_int32),
-                ("hist_dim", C.c_int32), ("num_actions", C.c_int32), ("num_priv", C.c_int32),
-                ("variant", C.c_int32), ("overflow", C.c_void_p), ("layers", _PolicyLayer * 11),
-                ("hist_ld", C.c_int64)]
+def lib():
+    """The HIP rollout library (libgo1_rollout.so), loaded once; NativeError when it is missing or another ABI."""
+    global _lib
+    if _lib is None:
+        _lib = native.load_library(LIB_PATH, "go1_rollout_abi_version", LA.GO1_ROLLOUT_ABI_VERSION,
+                                   "go1_rollout_last_error", LA.ROLLOUT_ARGTYPES)
+    return _lib
 
 
 def _pack_linear(lin):
@@ -132,44 +121,42 @@ class FusedPolicy:
     """ActorCritic forward for the rollout (act + evaluate) in one HIP kernel
     (csrc/rollout.hip policy_kernel).  Re-pack after every optimiser step."""
 
-    def __init__(self, ac, lib, variant=0):
+    def __init__(self, ac, variant=0):
         self.ac = ac
-        self.lib = lib
+        self.lib = lib()
+        self._forward = self.lib.go1_policy_forward
         self.packed = None
         self.variant = variant  # 0: per-net workgroups of 32 envs, 1: one workgroup of 16 envs (go1_policy_args)
+        dev = next(ac.parameters()).device
+        self._stream = native.raw_stream_of(dev)
         # workgroups that took the f32 fallback of the range guard (activations beyond f16's range)
-        self.overflow = torch.zeros(1, dtype=torch.int32, device=next(ac.parameters()).device)
+        self.overflow = torch.zeros(1, dtype=torch.int32, device=dev)
 
     @staticmethod
     def supported(ac):
         try:
-            a, p, c = ac.adaptation_module, ac.actor_body, ac.critic_body
-            shapes = [tuple(m.weight.shape) for m in (a[0], a[2], a[4], p[0], p[2], p[4], p[6], c[0], c[2], c[4],
-                                                       c[6])]
+            lin = LA.policy_linears(ac)
+            shapes = [tuple(m.weight.shape) for m in lin]
         except (IndexError, AttributeError):
             return False
-        h, npv = ac.num_obs_history, ac.num_privileged_obs
-        want = [(256, h), (128, 256), (npv, 128), (512, h + npv), (256, 512), (128, 256), (None, 128),
-                (512, h + npv), (256, 512), (128, 256), (1, 128)]
-        ok = all(w[0] in (None, s[0]) and w[1] == s[1] for s, w in zip(shapes, want))
+        h, npv, na = ac.num_obs_history, ac.num_privileged_obs, shapes[6][0]
         # any history width for the default launch (inputs streamed in chunks of 288), as long as the
         # 32-wide groups that hold the latent sit in the last chunk (go1_policy_forward checks the same)
         kin, gl, GL = h + npv, h // 32, -(-(h + npv) // 32)
         g_last = 9 * (-(-GL // 9) - 1)
-        return (ok and 1 <= npv <= 8 and kin <= 16384 and gl >= g_last and shapes[6][0] <= 16
-                and isinstance(a[1], nn.ELU))
+        return (shapes == LA.policy_shapes(h, npv, na) and 1 <= npv <= 8 and kin <= 16384 and gl >= g_last
+                and na <= 16 and isinstance(ac.adaptation_module[1], nn.ELU))
 
     def pack(self):
         ac = self.ac
-        mods = [ac.adaptation_module[i] for i in (0, 2, 4)] + [ac.actor_body[i] for i in (0, 2, 4, 6)] + \
-               [ac.critic_body[i] for i in (0, 2, 4, 6)]
+        mods = LA.policy_linears(ac)
         self.packed = [_pack_linear(m) for m in mods]
         # the unsplit f32 weights for the range guard's fallback (the module's own tensors: an optimiser
         # step updates them in place; the split copies are re-packed)
         self.wf = [m.weight.detach().float().contiguous() for m in mods]
-        self.na = ac.actor_body[6].out_features
+        self.na = mods[6].out_features
         self.np = ac.num_privileged_obs
-        self.args = _PolicyArgs(num_actions=self.na, num_priv=self.np, overflow=self.overflow.data_ptr())
+        self.args = LA.PolicyArgs(num_actions=self.na, num_priv=self.np, overflow=self.overflow.data_ptr())
         for i, (w, b) in enumerate(self.packed):
             self.args.layers[i].w, self.args.layers[i].b = w.data_ptr(), b.data_ptr()
             self.args.layers[i].wf = self.wf[i].data_ptr()
@@ -208,9 +195,9 @@ class FusedPolicy:
             out = out + (actions, sigma, logp)
         else:
             a.actions = None
-        rc = self.lib.go1_policy_forward(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc != 0:
-            raise RuntimeError(self.lib.go1_rollout_last_error().decode())
+        rc = self._forward(C.byref(a), self._stream())
+        if rc:
+            native.check(self.lib, rc)
         return out
 
 
@@ -218,25 +205,10 @@ class HipRolloutKernels:
     """ctypes binding of libgo1_rollout.so; raises when the library or the GPU is missing."""
 
     def __init__(self):
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"HIP rollout library missing: {LIB_PATH} (run __graft_entry__.build())")
+        self.lib = lib()
+        self._record = self.lib.go1_record_transition
         if not torch.cuda.is_available():
-            raise RuntimeError("no GPU visible: the rollout kernels have no CPU fallback")
-        lib = C.CDLL(LIB_PATH)
-        lib.go1_rollout_last_error.restype = C.c_char_p
-        lib.go1_record_transition.argtypes = [C.POINTER(_Transition), C.c_int32, C.c_float, C.c_void_p]
-        lib.go1_gae.argtypes = [C.c_void_p] * 7 + [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p]
-        lib.go1_adv_normalize.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_void_p]
-        lib.go1_policy_forward.argtypes = [C.POINTER(_PolicyArgs), C.c_void_p]
-        self.lib = lib
-
-    def _chk(self, rc):
-        if rc != 0:
-            raise RuntimeError(self.lib.go1_rollout_last_error().decode())
-
-    @staticmethod
-    def _s():
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            raise native.NativeError("no GPU visible: the rollout kernels have no CPU fallback")
 
     _SRC = (("obs", "observations"), ("privileged_obs", "privileged_observations"),
             ("obs_history", "observation_histories"), ("actions", "actions"), ("mu", "action_mean"),
@@ -246,7 +218,8 @@ class HipRolloutKernels:
     def record(self, st, step, tr, gamma):
         t = getattr(st, "_tr_struct", None)
         if t is None:
-            t = st._tr_struct = _Transition()
+            t = st._tr_struct = LA.Transition()
+            st._tr_stream = native.raw_stream_of(st.observations.device)
             t.num_obs, t.num_priv = st.observations.shape[-1], st.privileged_observations.shape[-1]
             t.num_obs_history, t.num_actions = st.observation_histories.shape[-1], st.actions.shape[-1]
             st._tr_dst = [(k, buf) for k, buf in (
@@ -274,21 +247,25 @@ class HipRolloutKernels:
             setattr(t, k, buf[step].data_ptr())
         d = tr.get("time_outs_deferred")  # (flag, pending, dst) device pointers, or None
         t.time_outs_flag, t.time_outs_pending, t.time_outs_dst = d if d is not None else (None, None, None)
-        self._chk(self.lib.go1_record_transition(C.byref(t), st.num_envs, gamma, self._s()))
+        rc = self._record(C.byref(t), st.num_envs, gamma, st._tr_stream())
+        if rc:
+            native.check(self.lib, rc)
         return keep
 
     def gae(self, st, last_values, gamma, lam):
         lv = last_values.detach().contiguous()
-        self._chk(self.lib.go1_gae(st.rewards.data_ptr(), st.dones.data_ptr(), st.values.data_ptr(), lv.data_ptr(),
-                                   st.returns.data_ptr(), st.advantages.data_ptr(), st.adv_stats.data_ptr(),
-                                   st.num_transitions_per_env, st.num_envs, gamma, lam, self._s()))
+        native.check(self.lib, self.lib.go1_gae(
+            st.rewards.data_ptr(), st.dones.data_ptr(), st.values.data_ptr(), lv.data_ptr(), st.returns.data_ptr(),
+            st.advantages.data_ptr(), st.adv_stats.data_ptr(), st.num_transitions_per_env, st.num_envs, gamma, lam,
+            native.raw_stream(st.rewards.device)))
 
     def policy(self, ac):
-        return FusedPolicy(ac, self.lib) if FusedPolicy.supported(ac) else None
+        return FusedPolicy(ac) if FusedPolicy.supported(ac) else None
 
     def normalize(self, st, count):
-        self._chk(self.lib.go1_adv_normalize(st.advantages.data_ptr(), st.adv_stats.data_ptr(), float(count),
-                                             st.advantages.numel(), self._s()))
+        native.check(self.lib, self.lib.go1_adv_normalize(st.advantages.data_ptr(), st.adv_stats.data_ptr(),
+                                                          float(count), st.advantages.numel(),
+                                                          native.raw_stream(st.advantages.device)))
 
 
 # ----------------------------------------------------------------------------- model
@@ -300,33 +277,17 @@ def get_activation(name):
     return acts[name]()
 
 
-_COLSUM_LIB = []  # [ctypes lib or None], loaded on first use
-
-
 def _colsum(g):
     """Column sums of a (rows, cols) gradient (the bias gradient) with the deterministic HIP kernel
-    (go1_colsum); torch's sum(0) off the GPU or without the library."""
-    if not g.is_cuda or g.dim() != 2 or not g.is_contiguous() or g.dtype != torch.float32 or g.shape[0] < 64 or \
-            os.environ.get("GO1_COLSUM", "1") == "0":
-        return g.sum(0)
-    if not _COLSUM_LIB:
-        lib = None
-        if os.path.exists(LIB_PATH):
-            lib = C.CDLL(LIB_PATH)
-            lib.go1_colsum.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-            lib.go1_rollout_last_error.restype = C.c_char_p
-        _COLSUM_LIB.append(lib)
-    lib = _COLSUM_LIB[0]
-    if lib is None:
+    (go1_colsum); torch's sum(0) off the GPU and for what the kernel does not take."""
+    if not g.is_cuda or g.dim() != 2 or not g.is_contiguous() or g.dtype != torch.float32 or g.shape[0] < 64:
         return g.sum(0)
     rows, cols = g.shape
     parts = max(1, min(512 // ((cols + 63) // 64), rows // 256, 64))
     part = torch.empty((parts, cols), dtype=torch.float32, device=g.device)
     out = torch.empty(cols, dtype=torch.float32, device=g.device)
-    rc = lib.go1_colsum(g.data_ptr(), rows, cols, part.data_ptr(), parts, out.data_ptr(),
-                        C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(lib.go1_rollout_last_error().decode())
+    native.check(lib(), lib().go1_colsum(g.data_ptr(), rows, cols, part.data_ptr(), parts, out.data_ptr(),
+                                         native.raw_stream(g.device)))
     return out
 
 
@@ -569,15 +530,18 @@ class PPO:
         # tensor so that the adaptive schedule (ppo.py:124-136) runs on the device -- no host sync per
         # mini-batch; the rate is computed in f64 as the reference's Python floats are, and the f32 copy the
         # kernel reads is the value the foreach path would cast to.  On the CPU: the reference's path.
-        self._dev_lr = torch.device(device).type == "cuda" and os.environ.get("GO1_PPO_FUSED", "1") != "0"
+        self._dev_lr = torch.device(device).type == "cuda"
         params = list(self.actor_critic.parameters())
         # The mini-batch step (forward, backward, gradient clip, both Adam steps, the adaptive rate) is
         # captured once into a HIP graph and replayed for every later mini-batch (GO1_PPO_GRAPH=0: eager):
         # it is ~150 small launches whose host issue left the GPU idle between them.  One rank only (the
         # gradient all-reduce stays eager).
         self._graph_on = self._dev_lr and os.environ.get("GO1_PPO_GRAPH", "1") != "0"
-        self._graph = None
+        self._graph = self._graph_key = None
         self._graph_warm = 0
+        self._graph_idx = self._graph_acc = self._graph_draw = None  # static buffers of the captured step
+        self._side = None  # the one stream of warm-up and capture
+        self._engine = None  # ppo_engine.PPOEngine, created by the first update() that runs on it
         if self._dev_lr:
             self._lr64 = torch.tensor(PPO_Args.learning_rate, dtype=torch.float64, device=device)
             self._lr32 = torch.tensor(PPO_Args.learning_rate, dtype=torch.float32, device=device)
@@ -742,13 +706,12 @@ class PPO:
                     self._lr64.copy_(new)
                     self._lr32.copy_(new)
             else:
-                kl_mean = float(kl_mean)
+                kl_mean, lr = float(kl_mean), self.learning_rate
                 if kl_mean > A.desired_kl * 2.0:
-                    self.learning_rate = max(1e-5, self.learning_rate / 1.5)
+                    lr = max(1e-5, lr / 1.5)
                 elif A.desired_kl / 2.0 > kl_mean > 0.0:
-                    self.learning_rate = min(1e-2, self.learning_rate * 1.5)
-                for g in self.optimizer.param_groups:
-                    g["lr"] = self.learning_rate
+                    lr = min(1e-2, lr * 1.5)
+                self._set_lr(lr)
         ratio = torch.exp(logp_b - torch.squeeze(old_logp_b))
         surrogate = -torch.squeeze(adv_b) * ratio
         surrogate_clipped = -torch.squeeze(adv_b) * torch.clamp(ratio, 1.0 - A.clip_param, 1.0 + A.clip_param)
@@ -816,7 +779,7 @@ class PPO:
         # ac.act's unused sample per mini-batch, drawn before each step with the same shape: the same torch
         # generator advance as the eager loop's (the values are discarded there too)
         na = st.actions.shape[-1]
-        if getattr(self, "_graph_draw", None) is None or self._graph_draw[0].shape != (mb, na):
+        if self._graph_draw is None or self._graph_draw[0].shape != (mb, na):
             self._graph_draw = (torch.zeros(mb, na, device=self.device), torch.ones(mb, na, device=self.device))
 
         def step():
@@ -827,7 +790,7 @@ class PPO:
         # warm-up and capture run on ONE persistent side stream: the parameters' AccumulateGrad nodes are created
         # there and every later backward (warm-up, capture) runs on the same stream (a fresh stream per warm-up
         # mini-batch made torch warn about a stream mismatch of the accumulation)
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             self._side = torch.cuda.Stream(self.device)
         side = self._side
         for _ in range(A.num_learning_epochs):
@@ -865,49 +828,51 @@ class PPO:
         from . import ppo_engine
         return ppo_engine.supported(self.actor_critic)
 
+    def _set_lr(self, lr):
+        """The learning rate of PPO.optimizer, everywhere it is kept: the attribute, the param groups (a device
+        tensor with the fused Adam) and the device copies the adaptive schedule steps."""
+        self.learning_rate = lr
+        for g in self.optimizer.param_groups:
+            if isinstance(g["lr"], torch.Tensor):
+                g["lr"].fill_(lr)
+            else:
+                g["lr"] = lr
+        if self._dev_lr:
+            self._lr64.fill_(lr)
+            self._lr32.fill_(lr)
+
     def update(self):
         A = PPO_Args
         n_up = A.num_learning_epochs * A.num_mini_batches
         n_ad = n_up * A.num_adaptation_module_substeps
         if self._engine_on() and A.num_adaptation_module_substeps == 1:
             from . import ppo_engine
-            if getattr(self, "_engine", None) is None:
+            if self._engine is None:
                 self._engine = ppo_engine.PPOEngine(self)
             sums, lr = self._engine.update(A, A.num_mini_batches, A.num_learning_epochs, _world(),
                                            use_graph=self._graph_on,
                                            split=os.environ.get("GO1_PPO_SPLIT", "0") == "1")
-            self.learning_rate = lr
-            for g in self.optimizer.param_groups:
-                if isinstance(g["lr"], torch.Tensor):
-                    g["lr"].fill_(lr)
-                else:
-                    g["lr"] = lr
-            if self._dev_lr:
-                self._lr64.fill_(lr)
-                self._lr32.fill_(lr)
-            self.storage.clear()
-            if self.fused is not None:
-                self.fused.pack()  # the rollout kernel reads the updated weights
-            return (sums[0] / n_up, sums[1] / n_up, sums[2] / n_ad, 0.0, 0.0, sums[3] / n_ad, 0.0, 0.0)
-        if getattr(self, "_engine", None) is not None:
-            self._engine.release_optimizer_state()  # torch's Adam steps per-parameter state of its own
-        # the loss means accumulate on the device (ppo.py:186-187, 200-201 call .item() per mini-batch:
-        # a host sync each); one copy at the end.
-        acc = torch.zeros(4, dtype=torch.float32, device=self.device)  # value, surrogate, adapt, adapt_test
-        if self._graph_on and _world() == 1:
-            self._graphed_minibatches(acc)
+            self._set_lr(lr)
         else:
-            gen = self.storage.mini_batch_generator(A.num_mini_batches, A.num_learning_epochs)
-            for b in gen:
-                self._minibatch_step(b[:11], acc)
+            if self._engine is not None:
+                self._engine.release_optimizer_state()  # torch's Adam steps per-parameter state of its own
+            # the loss means accumulate on the device (ppo.py:186-187, 200-201 call .item() per mini-batch:
+            # a host sync each); one copy at the end.
+            sums = torch.zeros(4, dtype=torch.float32, device=self.device)  # value, surrogate, adapt, adapt_test
+            if self._graph_on and _world() == 1:
+                self._graphed_minibatches(sums)
+            else:
+                gen = self.storage.mini_batch_generator(A.num_mini_batches, A.num_learning_epochs)
+                for b in gen:
+                    self._minibatch_step(b[:11], sums)
         self.storage.clear()
         if self.fused is not None:
             self.fused.pack()  # the rollout kernel reads the updated weights
-        mean_value_loss, mean_surrogate_loss, mean_adapt, mean_adapt_test = (float(x) for x in acc.cpu())
-        if self._dev_lr:
-            self.learning_rate = float(self._lr64)
-        return (mean_value_loss / n_up, mean_surrogate_loss / n_up, mean_adapt / n_ad, 0.0, 0.0,
-                mean_adapt_test / n_ad, 0.0, 0.0)
+        if isinstance(sums, torch.Tensor):  # the torch path's device sums, read once the pack is queued
+            sums = sums.cpu().tolist()
+            if self._dev_lr:
+                self.learning_rate = float(self._lr64)
+        return (sums[0] / n_up, sums[1] / n_up, sums[2] / n_ad, 0.0, 0.0, sums[3] / n_ad, 0.0, 0.0)
 
 
 # ----------------------------------------------------------------------------- runner

@@ -6,7 +6,8 @@ out, to price it in situ) and the timing / accounting builds (GO1_STAMPS: s_memt
 tools/stamps.py; GO1_ISA_MARKS: section markers for tools/isa_sections.py).  Variants that were
 measured and rejected are deleted from the source, not kept behind switches.  A front-end pass
 (hipcc -fsyntax-only, host and gfx950 device) per variant keeps them from rotting.  go1_velocity.hip
-has the curriculum launch's stamps (GO1_VEL_STAMPS, tools/vel_stamps.py)."""
+has the curriculum launch's stamps (GO1_VEL_STAMPS, tools/vel_stamps.py); rollout.hip and ppo_update.hip keep their
+stamp builds only (GO1_POLICY_STAMPS, tools/policy_stamps.py; PPO_STAMPS, tools/xw_stamps.py)."""
 import os
 import re
 import shutil
@@ -20,6 +21,9 @@ CSRC = os.path.join(ROOT, "legged_tracking_amd", "csrc")
 SRC = os.path.join(CSRC, "go1_step.hip")
 SCANNED = [SRC, os.path.join(CSRC, "go1_device.h"), os.path.join(CSRC, "go1_step_shared.h")]
 VEL_SRC = os.path.join(CSRC, "go1_velocity.hip")
+ROLLOUT_SRC = os.path.join(CSRC, "rollout.hip")
+PPO_SRC = os.path.join(CSRC, "ppo_update.hip")
+INC = os.path.join(ROOT, "include")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -34,12 +38,21 @@ def test_only_diagnostic_switches_remain():
     allowed = {"GO1_STAMPS", "GO1_ISA_MARKS", "GO1_VEL_STAMPS", "GO1_DEVICE_H"}
     stray = {c for c in conds if c.startswith("GO1_") and c not in allowed and not c.startswith("GO1_ABL_")}
     assert not stray, f"variant switches outside the diagnostic set: {sorted(stray)}"
+    # the learn libraries and their headers: the two stamp builds and the header guards, nothing else
+    learn = "".join(open(f).read() for f in (ROLLOUT_SRC, PPO_SRC, os.path.join(INC, "go1_rollout.h"),
+                                             os.path.join(INC, "go1_ppo.h")))
+    conds = set(re.findall(r"#\s*(?:if|ifdef|ifndef|elif)\s+!?\s*(?:defined\s*\(?\s*)?(\w+)", learn))
+    allowed = {"GO1_POLICY_STAMPS", "PPO_STAMPS", "GO1_ROLLOUT_H", "GO1_PPO_H"}
+    stray = {c for c in conds if c.startswith(("GO1_", "PPO_")) and c not in allowed}
+    assert {"GO1_POLICY_STAMPS", "PPO_STAMPS"} <= conds and not stray, \
+        f"variant switches in rollout.hip / ppo_update.hip: {sorted(stray)}"
 
 
 @pytest.mark.skipif(not shutil.which(HIPCC) and not os.path.exists(HIPCC), reason="hipcc not available")
 def test_diagnostic_builds_compile():
     variants = [([], SRC)] + [([f"-D{s}"], SRC) for s in _switches()] + [(["-DGO1_VEL_STAMPS"], VEL_SRC)]
     assert len(variants) >= 10  # 8 ablations + stamps / ISA marks + the velocity stamps
+    variants += [(["-DGO1_POLICY_STAMPS"], ROLLOUT_SRC), (["-DPPO_STAMPS"], PPO_SRC)]
 
     def one(v):
         flags, src = v

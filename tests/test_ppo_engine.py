@@ -17,7 +17,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from legged_tracking_amd import ppo_engine as PE, rollout as R  # noqa: E402
+from legged_tracking_amd import learn_abi as LA, ppo_engine as PE, rollout as R  # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "go1_ppo.h")
@@ -33,7 +33,7 @@ def test_library_exports_every_go1_ppo_symbol_and_layout_matches_module():
     for hist, priv, na in ((261, 2, 12), (2100, 2, 12), (1020, 6, 12), (70, 8, 16)):
         ac = R.ActorCritic(70, priv, hist, na)
         assert PE.supported(ac)
-        d = PE._Dims(hist=hist, priv=priv, actions=na, mb=384, rows=1536)
+        d = LA.PPODims(hist=hist, priv=priv, actions=na, mb=384, rows=1536)
         tot, ad = C.c_int64(), C.c_int64()
         assert lib.go1_ppo_param_count(C.byref(d), C.byref(tot), C.byref(ad)) == 0
         sd = dict(ac.named_parameters())
@@ -41,15 +41,15 @@ def test_library_exports_every_go1_ppo_symbol_and_layout_matches_module():
         assert ad.value == sum(p.numel() for p in ac.adaptation_module.parameters())
         nb = C.c_int64()
         assert lib.go1_ppo_workspace_bytes(C.byref(d), C.byref(nb)) == 0 and nb.value > 0
-    bad = PE._Dims(hist=261, priv=9, actions=12, mb=384, rows=1536)
+    bad = LA.PPODims(hist=261, priv=9, actions=12, mb=384, rows=1536)
     assert lib.go1_ppo_param_count(C.byref(bad), None, None) == -1
     assert b"priv 1..8" in lib.go1_ppo_last_error()
     # mb < 5 leaves the adaptation loss no training row (num_train = mb // 5 * 4): go1_ppo_grad refuses it before
     # it touches a buffer; the layout queries (PPOEngine.__init__ asks with mb = 1) accept it
-    few = PE._Dims(hist=261, priv=2, actions=12, mb=4, rows=1536)
+    few = LA.PPODims(hist=261, priv=2, actions=12, mb=4, rows=1536)
     assert lib.go1_ppo_param_count(C.byref(few), None, None) == 0
     for phase in (0, 1):
-        assert lib.go1_ppo_grad(C.byref(few), C.byref(PE._Bufs()), phase, None) == -1
+        assert lib.go1_ppo_grad(C.byref(few), C.byref(LA.PPOBufs()), phase, None) == -1
         assert b"mb >= 5" in lib.go1_ppo_last_error()
     # a module the engine does not implement (another activation) falls back to the torch update
     R.AC_Args.activation = "tanh"

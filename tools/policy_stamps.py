@@ -42,13 +42,13 @@ def main():
         for _ in range(5):
             alg.act(obs, priv, obs)
     torch.cuda.synchronize()
-    lib = alg.fused.lib
+    lib = R.lib()
     buf = np.zeros(512 * 16 * 12, np.uint64)
     assert lib.go1_policy_stamps(buf.ctypes.data_as(C.c_void_p), C.c_size_t(buf.nbytes)) == 0
     t_full = buf.reshape(512, 16, 12).astype(np.int64)[:256]
     t_all = t_full[:, :, :9]
     used = t_all[:, 0, 0] != 0  # workgroups of the launch (the stamp buffer holds 256)
-    na = -(-n // (16 * int(os.environ.get("GO1_SPLIT_ET_A", "2"))))
+    na = -(-n // (16 * 2))  # actor workgroups: SPLIT_ET_A = 2 env tiles each (rollout.hip)
     groups = [("all", t_all[used])] if variant else [("actor workgroups", t_all[:na][used[:na]]),
                                                      ("critic workgroups", t_all[na:][used[na:]])]
     for label, t in groups:
