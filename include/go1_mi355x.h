@@ -10,6 +10,10 @@
  *                          :1311-1320, gym.set_dof_actuation_force_tensor /
  *                          simulate / fetch_results / refresh_dof_state_tensor
  *                          :82-88, post_physics_step :114-169)
+ *                         the height scan (_init_height_points :1902-1916, _get_heights :1918-1965,
+ *                          the height block of compute_observations :388-423) over any
+ *                          measured_points_x x measured_points_y grid up to GO1_MAX_SCAN_X x
+ *                          GO1_MAX_SCAN_Y (go1_config.scan_nx / scan_ny / scan_x / scan_y, go1_scan_mode)
  *   go1_reset_idx()   <- LeggedRobot.reset_idx(env_ids)        :218-296
  *   go1_reset_envs()     (the same, env ids as a mask)
  *                         (+ gym.set_*_tensor_indexed :1011-1013, :1050-1052)
@@ -36,7 +40,7 @@
 extern "C" {
 #endif
 
-#define GO1_ABI_VERSION 6
+#define GO1_ABI_VERSION 7
 
 #define GO1_NUM_DOF 12
 #define GO1_NUM_BODIES 17
@@ -57,6 +61,12 @@ extern "C" {
 #define GO1_ACTUATOR_FLOATS 1313 /* w1[32][6] b1[32] w2[32][32] b2[32] w3[32] b3[1] */
 #define GO1_GRID_X 21
 #define GO1_GRID_Y 11
+/* The height scan's point counts (Cfg.terrain.measured_points_x / _y, _init_height_points :1902-1916) are
+ * run-time: go1_config.scan_nx x scan_ny up to these caps (61 x 31 is the reference's ppo_cse_cnn map).
+ * GO1_GRID_X x GO1_GRID_Y, the README grid, is the one count pair with step kernels that keep the scan in
+ * registers; every other pair runs the streamed kernel (go1_scan_mode). */
+#define GO1_MAX_SCAN_X 64
+#define GO1_MAX_SCAN_Y 32
 #define GO1_AUX 32         /* base lin vel 3, base ang vel 3, commands 2, foot pos 12, torques 12 */
 /* Episode-log row (go1_step_args.episode_log): n_terms + 3 episode sums, episode length,
  * reached, goal distance -> width n_terms + 6. */
@@ -135,7 +145,9 @@ typedef struct go1_config {
   int32_t rotate_camera;       /* camera pitch 0 in the height scan (:1934-1936) */
   int32_t observe_heights;     /* (:388) */
   int32_t timestep_in_obs;     /* episode_length / max_episode_length after the actions (:375-377) */
-  int32_t num_obs;             /* obs row width: 41 + timestep_in_obs + 2 x scanned points */
+  int32_t num_obs;             /* obs row width: 41 + timestep_in_obs + 2 x scanned points; scanned points =
+                                  (scan_nx - x_start) * scan_ny, x_start = scan_nx / 2 + 1 with
+                                  measure_front_half (:395-399), else 0 */
   int32_t u_per_env;           /* parity-mode uniform row width: GO1_U_NOISE + num_obs + trajectory draws */
   int32_t traj_kind;           /* 0 fixed_target, 1 random_target, 2 random_goal (trajectory_function.py) */
   int32_t traj_length;         /* waypoints per env, <= GO1_MAX_TRAJ */
@@ -184,7 +196,8 @@ typedef struct go1_config {
   float dof_pos_limits[24];    /* soft limits (lo, hi) per dof (:702-706) */
   float torque_limits[12];
   float hard_limits[24];       /* URDF limits for the native joint-limit model */
-  float height_grid_x[GO1_GRID_X], height_grid_y[GO1_GRID_Y];
+  float height_grid_x[GO1_GRID_X], height_grid_y[GO1_GRID_Y]; /* the scan coordinates of a 21 x 11 grid (the
+                                  register-resident kernels read these; scan_x / scan_y below hold them too) */
   /* native contact / joint-limit model (no reference equivalent: PhysX is closed) */
   float contact_stiffness, contact_damping, friction_damping, limit_stiffness, limit_damping;
   /* restitution (PhysX's restitution with the default average combine and bounce threshold): a point
@@ -198,6 +211,11 @@ typedef struct go1_config {
   float self_stiffness, self_damping;
   float model[GO1_MODEL_FLOATS];
   float actuator[GO1_ACTUATOR_FLOATS];
+  /* height-scan grid of any size: measured_points_x / _y (:1902-1916), 1 <= scan_nx <= GO1_MAX_SCAN_X,
+   * 1 <= scan_ny <= GO1_MAX_SCAN_Y, at least one scanned row; with scan_nx x scan_ny = 21 x 11 the first 21 / 11
+   * entries must equal height_grid_x / _y */
+  int32_t scan_nx, scan_ny;
+  float scan_x[GO1_MAX_SCAN_X], scan_y[GO1_MAX_SCAN_Y];
 } go1_config;
 
 /* Per-env state, SoA planes, each row-major (n_envs, width).  f32 unless noted. */
@@ -263,7 +281,7 @@ typedef struct go1_step_args {
   float* contact_forces;       /* (n_envs, 17, 3) or NULL */
   /* optional debug outputs (NULL = not written) */
   float* dbg_torques;          /* (decimation, n_envs, 12) */
-  float* dbg_heights;          /* (n_envs, 2, 21, 11) measured heights before camera_zero */
+  float* dbg_heights;          /* (n_envs, 2, scan_nx, scan_ny) measured heights before camera_zero */
   float* dbg_terms;            /* (n_envs, GO1_MAX_TERMS) unscaled reward terms, slot order */
   float* dbg_commands;         /* (n_envs, 2) */
   uint8_t* dbg_reached;        /* (n_envs) */
@@ -383,6 +401,15 @@ int go1_step(go1_handle* h, const go1_step_args* args, void* stream);
  * config that does not match.  go1_is_specialized returns 1 when the specialised kernel runs. */
 int go1_specialize(go1_handle* h, int enable);
 int go1_is_specialized(go1_handle* h);
+/* Height-scan path.  A 21 x 11 grid (GO1_GRID_X x GO1_GRID_Y) runs the kernels that gather the scan into
+ * registers right after the physics; any other scan_nx x scan_ny runs the streamed kernel, which samples, transforms
+ * and stores 16 points per env at a time in the epilogue, grid coordinates from go1_config.scan_x / scan_y.  Both
+ * compute identical results.  streamed = 1 forces the streamed kernel on a 21 x 11 handle (it then never runs the
+ * specialised one); streamed = 0 selects the register-resident kernels again and fails (GO1_E_ARG) for any other
+ * grid.  go1_is_streamed returns 1 when the streamed kernel runs.  n_envs: a multiple of 16 for a 21 x 11 handle
+ * (go1_create); the streamed kernel takes any count (the spare lanes of its last wave mirror the last env). */
+int go1_scan_mode(go1_handle* h, int streamed);
+int go1_is_streamed(go1_handle* h);
 /* extras["time_outs"] (:289-291) is rebound to time_out only on steps with a reset.  The
  * rebinding for step k is applied by the kernel of step k+1 (no launch of its own); call
  * this to have extras_time_outs of the last go1_step current now (one tiny launch,

@@ -5,7 +5,7 @@ checks sizes and offsets against the compiled library's expectations.
 """
 import ctypes as C
 
-GO1_ABI_VERSION = 6
+GO1_ABI_VERSION = 7
 GO1_NUM_DOF = 12
 GO1_NUM_BODIES = 17
 GO1_MAX_TERMS = 16
@@ -23,6 +23,8 @@ GO1_MODEL_FLOATS = 178
 GO1_ACTUATOR_FLOATS = 1313
 GO1_GRID_X = 21
 GO1_GRID_Y = 11
+GO1_MAX_SCAN_X = 64  # caps of the run-time scan grid (go1_config.scan_nx / scan_ny)
+GO1_MAX_SCAN_Y = 32
 GO1_AUX = 32
 
 # enum go1_term (include/go1_mi355x.h)
@@ -80,6 +82,7 @@ class Go1Config(C.Structure):
         ("limit_damping", F), ("terrain_restitution", F), ("bounce_threshold", F), ("self_stiffness", F),
         ("self_damping", F),
         ("model", F * GO1_MODEL_FLOATS), ("actuator", F * GO1_ACTUATOR_FLOATS),
+        ("scan_nx", I32), ("scan_ny", I32), ("scan_x", F * GO1_MAX_SCAN_X), ("scan_y", F * GO1_MAX_SCAN_Y),
     ]
 
 

@@ -845,13 +845,44 @@ def obs_layout(cfg):
     gravity 3, commands 2, dof pos 12, dof vel 12, actions 12, [timestep 1], [heights 2 x points]."""
     ts = int(bool(_get(cfg, "env.timestep_in_obs", False)))
     heights = bool(_get(cfg, "env.observe_heights", True))
-    rows = GO1_GRID_ROWS_FRONT if _get(cfg, "terrain.measure_front_half", True) else 21
-    n_pts = rows * 11
+    g = scan_grid(cfg)
+    n_pts = g["rows"] * g["ny"]
     width = 41 + ts + (2 * n_pts if heights else 0)
     return {"timestep": ts, "heights": heights, "n_points": n_pts, "height_offset": 41 + ts, "width": width}
 
 
-GO1_GRID_ROWS_FRONT = 10  # x rows 11..20 of the 21-row grid (:395-399)
+GO1_GRID_ROWS_FRONT = 10  # x rows 11..20 of the README's 21-row grid (:395-399)
+
+
+def scan_grid(cfg):
+    """The height scan of _init_height_points (:1902-1916): Cfg.terrain.measured_points_x / _y as f64 arrays,
+    their counts, the first observed x row (x_start = nx // 2 + 1 with measure_front_half, :395-399) and the
+    number of observed rows.  Raises, before any handle is built, for a grid the step does not take or the
+    reference itself fails on."""
+    x = np.asarray(_get(cfg, "terrain.measured_points_x", np.linspace(-1, 1, 21)), np.float64).ravel()
+    y = np.asarray(_get(cfg, "terrain.measured_points_y", np.linspace(-0.5, 0.5, 11)), np.float64).ravel()
+    for name, v, cap in (("measured_points_x", x, abi.GO1_MAX_SCAN_X), ("measured_points_y", y, abi.GO1_MAX_SCAN_Y)):
+        if v.size == 0:
+            raise ValueError(f"Cfg.terrain.{name} is empty: the height scan needs at least one point per axis")
+        if v.size > cap:
+            raise NotImplementedError(f"Cfg.terrain.{name} has {v.size} points; the step takes at most {cap} "
+                                      f"(GO1_MAX_SCAN_X x GO1_MAX_SCAN_Y = {abi.GO1_MAX_SCAN_X} x "
+                                      f"{abi.GO1_MAX_SCAN_Y} for measured_points_x x measured_points_y)")
+    nx, ny = int(x.size), int(y.size)
+    front = bool(_get(cfg, "terrain.measure_front_half", True))
+    x_start = nx // 2 + 1 if front else 0
+    if nx - x_start < 1:
+        raise ValueError(f"Cfg.terrain.measure_front_half keeps rows {x_start} .. {nx - 1} of measured_points_x: "
+                         f"none of its {nx} rows (at least 3 are needed, :395-399)")
+    if front and nx % 2 == 0 and bool(_get(cfg, "env.observe_heights", True)) and \
+            bool(_get(cfg, "noise.add_noise", False)):
+        # _get_noise_scale_vec (:1123-1125) sizes the height noise for nx // 2 rows, the observation keeps
+        # nx - (nx // 2 + 1): the first compute_observations fails adding them (:472-473)
+        raise RuntimeError(f"Cfg.terrain.measured_points_x has an even count ({nx}) with measure_front_half and "
+                           f"noise.add_noise: the reference's noise vector covers {nx // 2} rows of the scan, the "
+                           f"observation {nx - x_start} (:1123-1125 against :395-399); use an odd count or turn "
+                           f"the noise off")
+    return {"x": x, "y": y, "nx": nx, "ny": ny, "x_start": x_start, "rows": nx - x_start}
 
 
 def traj_draws(cfg):
@@ -913,8 +944,11 @@ def build_abi_config(cfg, n_envs=None, physics=None, actuator=None, hf_shape=(80
     ol = obs_layout(cfg)
     if int(cfg.env.num_observations) != ol["width"]:
         # compute_observations asserts the width (:475)
+        g = scan_grid(cfg)
         raise AssertionError(f"Observation shape ({n}, {ol['width']}) does not match num_observations "
-                             f"{cfg.env.num_observations}")
+                             f"{cfg.env.num_observations} ({ol['height_offset']} columns + 2 x {g['rows']} x "
+                             f"{g['ny']} scanned points of the {g['nx']} x {g['ny']} measured_points grid"
+                             f"{'' if ol['heights'] else ', not observed'})")
     c.num_obs = ol["width"]
     c.observe_heights = int(ol["heights"])
     c.timestep_in_obs = ol["timestep"]
@@ -1029,10 +1063,17 @@ def build_abi_config(cfg, n_envs=None, physics=None, actuator=None, hf_shape=(80
         c.torque_limits[i] = f32(L.TORQUE_LIMIT)
         lo, hi = L.JOINT_LIMITS[i % 3]
         c.hard_limits[2 * i], c.hard_limits[2 * i + 1] = f32(lo), f32(hi)
-    for i, v in enumerate(np.asarray(t.measured_points_x, np.float64)):
-        c.height_grid_x[i] = f32(v)
-    for i, v in enumerate(np.asarray(t.measured_points_y, np.float64)):
-        c.height_grid_y[i] = f32(v)
+    g = scan_grid(cfg)
+    c.scan_nx, c.scan_ny = g["nx"], g["ny"]
+    for i, v in enumerate(g["x"]):
+        c.scan_x[i] = f32(v)
+    for i, v in enumerate(g["y"]):
+        c.scan_y[i] = f32(v)
+    if (g["nx"], g["ny"]) == (abi.GO1_GRID_X, abi.GO1_GRID_Y):  # the register-resident kernels' block
+        for i, v in enumerate(g["x"]):
+            c.height_grid_x[i] = f32(v)
+        for i, v in enumerate(g["y"]):
+            c.height_grid_y[i] = f32(v)
     set_contact_fields(c, cfg, physics)
     for i, v in enumerate(M.model_block()):
         c.model[i] = float(v)

@@ -156,6 +156,9 @@ template <bool INJ, int KPTS, bool SPEC>
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) void go1_step_kernel(
     const go1_config* __restrict__ c_gen, KArgs K) {
   CCfg* __restrict__ c = (CCfg*)c_gen;
+  // KPTS == 0: the streamed height scan (any go1_config.scan_nx x scan_ny; go1_create / go1_scan_mode select it)
+  constexpr bool STREAM = KPTS == 0;
+  static_assert(!(STREAM && SPEC), "the specialised kernel keeps the README grid's scan in registers");
   const go1_state& st = K.st;
   const go1_step_args& A = K.a;
   const int n = c->n_envs;
@@ -165,7 +168,12 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // the 16 x 4 MFMA B operand, so the actuator-net inputs and outputs never move
   const int role = lane >> 4, el = (lane >> 2) & 3, sub16 = 4 * role + leg;
   const bool owner = role == 0;  // the lane of a leg that stores its per-leg outputs
-  const int e = blockIdx.x * SEPB + el;  // n % 16 == 0 (go1_create): every wave is full
+  // n % 16 == 0 (go1_create): every wave is full.  The streamed kernel alone also takes any other n_envs: the
+  // lanes of its last wave beyond n_envs mirror env n_envs - 1 (`dup`: the same loads, the same values stored to
+  // the same addresses, after every load of the wave), and keep out of the atomics and the compact log
+  const int e_raw = blockIdx.x * SEPB + el;
+  const bool dup = STREAM && e_raw >= n;
+  const int e = STREAM ? min(e_raw, n - 1) : e_raw;
   (void)n;
 #ifdef GO1_STAMPS
   s_go1_stamp_k = 0;
@@ -380,8 +388,14 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
   auto sample = [&](int i, int j, float& h0, float& h1) {
     if (hplane) { h0 = 1.0f; h1 = 0.0f; return; }
-    float px = s_phys[LDS_GX + i] + scan_x;
-    float py = s_phys[LDS_GY + j] + scan_y;
+    float px, py;
+    if constexpr (STREAM) {  // a grid of any size: its coordinates stay in the config (global memory)
+      px = c_gen->scan_x[i] + scan_x;
+      py = c_gen->scan_y[j] + scan_y;
+    } else {
+      px = s_phys[LDS_GX + i] + scan_x;
+      py = s_phys[LDS_GY + j] + scan_y;
+    }
     if (CI(camera_zero)) { px = px + camx; py = py + camy; }
     px = px - org_x;
     py = py - org_y;
@@ -395,10 +409,13 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     h0 = T.tile[(size_t)ix * CI(hf_ny) + iy];
     h1 = T.tile[((size_t)CI(hf_nx) + ix) * CI(hf_ny) + iy];
   };
-  const int x_start = CI(measure_front_half) ? GO1_GRID_X / 2 + 1 : 0;
-  const int n_pts = (GO1_GRID_X - x_start) * GO1_GRID_Y;
-  // the env's 16 lanes take points sub16 + 16 k (KPTS = 7 for the 110 front-half points, 15 for all 231)
-  float hv[KPTS][2];
+  // scan grid: GO1_GRID_X x GO1_GRID_Y compiled in, or go1_config.scan_nx x scan_ny (streamed, KPTS == 0)
+  const int NX = STREAM ? c->scan_nx : GO1_GRID_X, NY = STREAM ? c->scan_ny : GO1_GRID_Y;
+  const int x_start = CI(measure_front_half) ? NX / 2 + 1 : 0;
+  const int n_pts = (NX - x_start) * NY;
+  // the env's 16 lanes take points sub16 + 16 k (KPTS = 7 for the 110 front-half points, 15 for all 231);
+  // the streamed kernel keeps none: its epilogue samples 16 points per env at a time
+  float hv[STREAM ? 1 : KPTS][2];
 #ifdef GO1_ABL_NO_SCAN  // ablation build only: no height-scan gathers
   const bool scan = false;
 #else
@@ -467,7 +484,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   if (!INJ) {
     diverged = state_diverged(root, q, qd);
     if (diverged) reset = true;
-    if (diverged && sub16 == 0 && A.diverged_count) atomicAdd((unsigned long long*)A.diverged_count, 1ull);
+    if (diverged && sub16 == 0 && !dup && A.diverged_count) atomicAdd((unsigned long long*)A.diverged_count, 1ull);
   }
 
   MARK(termination_done);
@@ -614,7 +631,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     if (live) my_sum = my_sum + r;
     if (global_buckets && live) {
       K.bucket_r[(size_t)e * GO1_MAX_TERMS + sub16] = r;
-      atomicAdd(K.bucket_sum + sub16, (double)r);
+      if (!dup) atomicAdd(K.bucket_sum + sub16, (double)r);
     }
   }
   // sign of each slot's scale, as a slot bitmask (every env of the wave has the same scales):
@@ -658,8 +675,8 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // at one atomic per wave; the host orders the rows by (tag, env) as the reference logs them
   int log_row = -1;
   if (compact) {
-    log_row = wave_alloc_row(reset && owner && leg == 0, A.episode_log_count, lane, 4 * el);  // lane 4 el: env el's role 0, leg 0
-    if (log_row >= A.episode_log_cap) log_row = -1;  // dropped; the count keeps it (the host reports overflow)
+    log_row = wave_alloc_row(reset && owner && leg == 0 && !dup, A.episode_log_count, lane, 4 * el);  // lane 4 el: env el's role 0, leg 0
+    if (log_row >= A.episode_log_cap || dup) log_row = -1;  // dropped; the count keeps it (the host reports overflow)
   }
   if (reset && A.episode_log && (!compact || log_row >= 0)) {
     // reset_idx logging (:256-271): pre-reset sums, episode length, reached, goal distance
@@ -753,37 +770,48 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int o_h = 41 + CI(timestep_in_obs);
     const float zroot = root[2];  // post-reset (:401)
     const float cam_z = pm_sinf(cam_p) * CI(camera_offset_norm);
+    auto put_height = [&](int p, int layer, float hh) {
+      if (CI(camera_zero)) {
+        hh = hh - zroot;
+        hh = hh - cam_z;
+        hh = clampf(hh, -0.3f, 0.3f);
+      } else {
+        hh = clampf(hh, 0.0f, CI(ceiling_height));
+        hh = hh / CI(ceiling_height);
+        hh = hh - 0.5f;
+      }
+      const float v = clampf(hh * CI(obs_scale_heights), -clip, clip);
+      o[o_h + layer * n_pts + p] = v;
+      if (oh) oh[o_h + layer * n_pts + p] = v;
+    };
+    if constexpr (STREAM) {
+      // streamed: 16 points per env and pass, sampled here at the captured post-physics, pre-reset pose
+      // (what the register-resident kernels gathered right after the physics), stored at once
+      for (int p = sub16; p < n_pts; p += 16) {
+        float h0, h1;
+        sample(x_start + p / NY, p % NY, h0, h1);
+        put_height(p, 0, h0);
+        put_height(p, 1, h1);
+      }
+    } else {
 #pragma unroll
-    for (int k = 0; k < KPTS; ++k) {
-      const int p = sub16 + 16 * k;
-      if (p < n_pts) {
+      for (int k = 0; k < KPTS; ++k) {
+        const int p = sub16 + 16 * k;
+        if (p < n_pts) {
 #pragma unroll
-        for (int layer = 0; layer < 2; ++layer) {
-          float hh = hv[k][layer];
-          if (CI(camera_zero)) {
-            hh = hh - zroot;
-            hh = hh - cam_z;
-            hh = clampf(hh, -0.3f, 0.3f);
-          } else {
-            hh = clampf(hh, 0.0f, CI(ceiling_height));
-            hh = hh / CI(ceiling_height);
-            hh = hh - 0.5f;
-          }
-          const float v = clampf(hh * CI(obs_scale_heights), -clip, clip);
-          o[o_h + layer * n_pts + p] = v;
-          if (oh) oh[o_h + layer * n_pts + p] = v;
+          for (int layer = 0; layer < 2; ++layer) put_height(p, layer, hv[k][layer]);
         }
       }
     }
   }
   MARK(heights_done);
   if (A.dbg_heights) {
-    float* od = A.dbg_heights + (size_t)e * 2 * GO1_GRID_X * GO1_GRID_Y;
-    for (int p = sub16; p < GO1_GRID_X * GO1_GRID_Y; p += 16) {
+    float* od = A.dbg_heights + (size_t)e * 2 * NX * NY;
+    for (int p = sub16; p < NX * NY; p += 16) {
       float h0, h1;
-      sample(p / GO1_GRID_Y, p % GO1_GRID_Y, h0, h1);
+      sample(p / NY, p % NY, h0, h1);
       od[p] = h0;
-      od[GO1_GRID_X * GO1_GRID_Y + p] = h1;
+      od[NX * NY + p] = h1;
     }
   }
   if (sub16 == 0) {
@@ -980,6 +1008,7 @@ struct go1_handle {
   double* d_bucket_sum = nullptr; // 2 banks x GO1_MAX_TERMS
   uint64_t count = 0;          // go1_step calls so far
   bool spec = false;           // every GO1_SPEC_FIELDS value matches: the specialised kernel runs
+  bool streamed = false;       // the streamed height scan runs (any grid but 21 x 11, or go1_scan_mode)
   const uint8_t* prev_time_out = nullptr;
   uint8_t* prev_extras = nullptr;
 };
@@ -1010,6 +1039,8 @@ static bool spec_match(const go1_config& c) {
   // loop itself stays run-time)
   return m && c.decimation == 4;
 }
+// the scan counts with kernels that keep the scan in registers (KPTS 7 / 15); any other grid is streamed
+static bool scan_compiled_in(const go1_config& c) { return c.scan_nx == GO1_GRID_X && c.scan_ny == GO1_GRID_Y; }
 
 static int fail(int code, const std::string& msg) {
   g_err = msg;
@@ -1056,7 +1087,8 @@ int go1_create(const go1_config* cfg, go1_handle** out) {
   if (cfg->terrain_kind == 1 && !(cfg->horizontal_scale >= 0.0499f))
     return fail(GO1_E_ARG, "go1_create: horizontal_scale < 0.05 m is not supported by the capsule contact search");
   if (cfg->rand_interval <= 0) return fail(GO1_E_ARG, "go1_create: rand_interval");
-  if (cfg->n_envs % EPB != 0)
+  // a partial last wave exists in the streamed kernel only (any scan grid but 21 x 11)
+  if (cfg->n_envs % EPB != 0 && scan_compiled_in(*cfg))
     return fail(GO1_E_ARG, "go1_create: n_envs must be a multiple of 16 (one wave = 16 envs x 4 legs)");
   if (cfg->n_terms < 0 || cfg->n_terms > GO1_MAX_TERMS) return fail(GO1_E_ARG, "go1_create: n_terms");
   for (int k = 0; k < cfg->n_terms; ++k)
@@ -1065,8 +1097,17 @@ int go1_create(const go1_config* cfg, go1_handle** out) {
   if (cfg->traj_length < 1 || cfg->traj_length > GO1_MAX_TRAJ || cfg->traj_kind < 0 || cfg->traj_kind > 2 ||
       (cfg->traj_kind == 1 && (cfg->traj_interp < 1 || cfg->traj_length % cfg->traj_interp != 0)))
     return fail(GO1_E_ARG, "go1_create: trajectory shape");
+  if (cfg->scan_nx < 1 || cfg->scan_nx > GO1_MAX_SCAN_X || cfg->scan_ny < 1 || cfg->scan_ny > GO1_MAX_SCAN_Y)
+    return fail(GO1_E_ARG, "go1_create: scan_nx x scan_ny must be within 1 x 1 .. GO1_MAX_SCAN_X x GO1_MAX_SCAN_Y");
+  if (cfg->measure_front_half && cfg->scan_nx < 3)
+    return fail(GO1_E_ARG, "go1_create: measure_front_half keeps no row of a scan with fewer than 3 x rows");
+  if (scan_compiled_in(*cfg) &&
+      (memcmp(cfg->scan_x, cfg->height_grid_x, sizeof(cfg->height_grid_x)) != 0 ||
+       memcmp(cfg->scan_y, cfg->height_grid_y, sizeof(cfg->height_grid_y)) != 0))
+    return fail(GO1_E_ARG, "go1_create: a 21 x 11 scan needs scan_x / scan_y equal to height_grid_x / height_grid_y");
   {
-    const int n_pts = (cfg->measure_front_half ? GO1_GRID_X - (GO1_GRID_X / 2 + 1) : GO1_GRID_X) * GO1_GRID_Y;
+    const int x_start = cfg->measure_front_half ? cfg->scan_nx / 2 + 1 : 0;
+    const int n_pts = (cfg->scan_nx - x_start) * cfg->scan_ny;
     const int width = 41 + (cfg->timestep_in_obs ? 1 : 0) + (cfg->observe_heights ? 2 * n_pts : 0);
     if (cfg->num_obs != width) return fail(GO1_E_ARG, "go1_create: num_obs does not match the observation layout");
     const int traj_u = cfg->traj_kind == 1 ? 6 * (cfg->traj_length / cfg->traj_interp + 1)
@@ -1089,7 +1130,8 @@ int go1_create(const go1_config* cfg, go1_handle** out) {
   go1_handle* h = new (std::nothrow) go1_handle();
   if (!h) return fail(GO1_E_ARG, "go1_create: out of host memory");
   h->cfg = *cfg;
-  h->spec = spec_match(*cfg);
+  h->streamed = !scan_compiled_in(*cfg);
+  h->spec = !h->streamed && spec_match(*cfg);
   hipError_t e1 = hipMalloc(&h->d_cfg, sizeof(go1_config));
   hipError_t e2 = hipMalloc(&h->d_flags, 3 * sizeof(int32_t));
   if (e1 != hipSuccess || e2 != hipSuccess) {
@@ -1156,13 +1198,16 @@ int go1_step(go1_handle* h, const go1_step_args* a, void* stream) {
   const int bank = (int)(h->count & 1);
   K.bucket_r = h->d_bucket_r;
   K.bucket_sum = h->d_bucket_sum ? h->d_bucket_sum + bank * GO1_MAX_TERMS : nullptr;
-  dim3 grid(n / SEPB), block(TPB);
+  dim3 grid((n + SEPB - 1) / SEPB), block(TPB);  // n % 16 == 0 but for the streamed kernel (go1_create)
   const bool full = !h->cfg.measure_front_half;  // 231 scanned points: 15 per lane instead of 7
   if (a->episode_log_count && (!a->episode_log || a->episode_log_cap < 0 || h->cfg.indefinite_slots))
     return fail(GO1_E_ARG, "go1_step: a compact episode log needs episode_log, a capacity >= 0 and no indefinite "
                            "reward slots (their bucket pass rewrites rows by env)");
   auto go = [&](auto kern) { launch_timed(kern, grid, block, s, a->ev_begin, a->ev_end, h->d_cfg, K); };
-  if (inj) {  // parity mode: the README configuration replays through the specialised kernel too
+  if (h->streamed) {  // any scan grid: no scan registers, the epilogue streams the points
+    if (inj) go(go1_step_kernel<true, 0, false>);
+    else go(go1_step_kernel<false, 0, false>);
+  } else if (inj) {  // parity mode: the README configuration replays through the specialised kernel too
     if (full) go(go1_step_kernel<true, 15, false>);
     else if (h->spec) go(go1_step_kernel<true, 7, true>);
     else go(go1_step_kernel<true, 7, false>);
@@ -1188,11 +1233,24 @@ int go1_step(go1_handle* h, const go1_step_args* a, void* stream) {
 int go1_specialize(go1_handle* h, int enable) {
   if (!h) return fail(GO1_E_ARG, "go1_specialize: null handle");
   if (enable && !spec_match(h->cfg)) return fail(GO1_E_ARG, "go1_specialize: the config differs from the specialised one (go1_spec.h)");
+  if (enable && h->streamed) return fail(GO1_E_ARG, "go1_specialize: the handle runs the streamed height scan (go1_scan_mode)");
   h->spec = enable != 0;
   return GO1_OK;
 }
 
 int go1_is_specialized(go1_handle* h) { return h && h->spec ? 1 : 0; }
+
+int go1_scan_mode(go1_handle* h, int streamed) {
+  if (!h) return fail(GO1_E_ARG, "go1_scan_mode: null handle");
+  if (!streamed && !scan_compiled_in(h->cfg))
+    return fail(GO1_E_ARG, "go1_scan_mode: only a 21 x 11 scan has register-resident kernels");
+  // (a 21 x 11 handle has n_envs % 16 == 0, go1_create: both paths take it)
+  h->streamed = streamed != 0;
+  h->spec = !h->streamed && spec_match(h->cfg);
+  return GO1_OK;
+}
+
+int go1_is_streamed(go1_handle* h) { return h && h->streamed ? 1 : 0; }
 
 int go1_sync_time_outs(go1_handle* h, void* stream) {
   if (!h) return fail(GO1_E_ARG, "go1_sync_time_outs: null handle");

@@ -70,6 +70,8 @@ _ARGTYPES = {
     "go1_destroy": [C.c_void_p],
     "go1_specialize": [C.c_void_p, C.c_int],
     "go1_is_specialized": [C.c_void_p],
+    "go1_scan_mode": [C.c_void_p, C.c_int],
+    "go1_is_streamed": [C.c_void_p],
     "go1_tunnel_tiles": [C.POINTER(abi.Go1TunnelParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "go1_tunnel_generate": [C.POINTER(abi.Go1TunnelSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
 }
@@ -336,6 +338,11 @@ class Go1Native(NativeHandle):
         else:
             a.inj_dof = a.inj_root = a.inj_contact = None
         self._check_out(a, out)
+        if debug and "heights" in debug and (tuple(debug["heights"].shape) !=
+                                             (self.n, 2, self.cfg.scan_nx, self.cfg.scan_ny) or
+                                             not debug["heights"].is_contiguous()):
+            raise NativeError(f"debug heights must be a contiguous (n_envs, 2, {self.cfg.scan_nx}, "
+                              f"{self.cfg.scan_ny}) tensor (go1_config.scan_nx x scan_ny)")
         for k, fld in (("torques", "dbg_torques"), ("heights", "dbg_heights"), ("terms", "dbg_terms"),
                        ("commands", "dbg_commands"), ("reached", "dbg_reached")):
             setattr(a, fld, debug[k].data_ptr() if debug and k in debug else None)
@@ -381,6 +388,15 @@ class Go1Native(NativeHandle):
     def specialized(self):
         return bool(self._lib.go1_is_specialized(self.h))
 
+    def scan_mode(self, streamed):
+        """Force the streamed height scan (True) on a 21 x 11 grid, or go back to the kernels that keep the
+        scan in registers (False; raises for any other grid, which only the streamed kernel takes)."""
+        self._check(self._lib.go1_scan_mode(self.h, int(bool(streamed))))
+
+    @property
+    def streamed(self):
+        return bool(self._lib.go1_is_streamed(self.h))
+
     def sync_time_outs(self):
         """Make extras_time_outs current for the last step (the rebinding of step k is
         otherwise applied by the kernel of step k+1)."""
@@ -416,8 +432,9 @@ class Go1Native(NativeHandle):
         return out
 
 
-def debug_buffers(n, decimation, device):
+def debug_buffers(n, decimation, device, grid=(abi.GO1_GRID_X, abi.GO1_GRID_Y)):
+    """The optional debug outputs of go1_step; `grid` = (go1_config.scan_nx, scan_ny) of the handle."""
     return dict(torques=torch.zeros((decimation, n, 12), device=device),
-                heights=torch.zeros((n, 2, 21, 11), device=device),
+                heights=torch.zeros((n, 2, int(grid[0]), int(grid[1])), device=device),
                 terms=torch.zeros((n, abi.GO1_MAX_TERMS), device=device), commands=torch.zeros((n, 2), device=device),
                 reached=torch.zeros(n, dtype=torch.uint8, device=device))
