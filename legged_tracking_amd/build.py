@@ -1,10 +1,11 @@
 """Build the HIP C-ABI libraries for gfx950 in-tree (legged_tracking_amd/_build)."""
 import os
+import re
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-INC = os.path.join(HERE, "..", "include")
+CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "_build")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off"]
@@ -15,36 +16,44 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp
 # code adds register-pair moves that cost more than they save (measured -3 %).
 STEP_FLAGS = ["-fno-slp-vectorize"]
 
-# name -> (sources, extra dependencies, extra flags)
+# name -> (sources, extra flags); the headers a library depends on are derived from its sources (lib_files)
 LIBS = {
-    "libgo1_mi355x.so": (["go1_step.hip", "go1_terrain.hip"],
-                         ["pmath.h", "go1_device.h", "go1_step_shared.h", "go1_model_consts.h", "go1_spec.h",
-                          os.path.join(INC, "go1_mi355x.h")], STEP_FLAGS),
-    "libgo1_rollout.so": (["rollout.hip"], [os.path.join(INC, "go1_rollout.h")], []),
-    "libgo1_ppo.so": (["ppo_update.hip"], [os.path.join(INC, "go1_ppo.h")], []),
+    "libgo1_mi355x.so": (["go1_step.hip", "go1_terrain.hip"], STEP_FLAGS),
+    "libgo1_rollout.so": (["rollout.hip"], []),
+    "libgo1_ppo.so": (["ppo_update.hip"], []),
     # kernel-argument preloading: the curriculum launch's leading scalar arguments arrive in SGPRs with the wave
     # (11.75-11.78 against 12.02-12.10 us average per launch, alternating runs of one session)
-    "libgo1_velocity.so": (["go1_velocity.hip"],
-                           ["pmath.h", "go1_device.h", "go1_step_shared.h", "go1_model_consts.h",
-                            os.path.join(INC, "go1_mi355x.h"), os.path.join(INC, "go1_velocity.h")],
-                           STEP_FLAGS + ["-mllvm", "-amdgpu-kernarg-preload-count=16"]),
+    "libgo1_velocity.so": (["go1_velocity.hip"], STEP_FLAGS + ["-mllvm", "-amdgpu-kernarg-preload-count=16"]),
     # the ray caster behind the recording API (render.py); it shares no file with the step libraries
-    "libgo1_render.so": (["go1_render.hip"], [os.path.join(INC, "go1_render.h")], []),
+    "libgo1_render.so": (["go1_render.hip"], []),
 }
 OUT = os.path.join(BUILD, "libgo1_mi355x.so")  # the step library (kept for callers of build())
 
 
-def _paths(name):
-    srcs, deps, _ = LIBS[name]
-    srcs = [os.path.join(HERE, "csrc", s) for s in srcs]
-    return srcs, srcs + [d if os.path.isabs(d) else os.path.join(HERE, "csrc", d) for d in deps]
+def include_closure(paths):
+    """The files and everything their quoted #include "..." lines reach, transitively, in first-reached order.
+    A text scan (conditional includes count too); system <...> headers are not followed."""
+    seen, todo = [], [os.path.normpath(p) for p in paths][::-1]
+    while todo:
+        f = todo.pop()
+        if f in seen:
+            continue
+        seen.append(f)
+        incs = re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', open(f).read(), re.M)
+        todo += [os.path.normpath(os.path.join(os.path.dirname(f), i)) for i in incs][::-1]
+    return seen
+
+
+def lib_files(name):
+    """Every file library `name` is made of: its sources and their include closure (csrc/ and include/)."""
+    return include_closure(os.path.join(CSRC, s) for s in LIBS[name][0])
 
 
 def needs_build(name):
     out = os.path.join(BUILD, name)
     if not os.path.exists(out):
         return True
-    return any(os.path.getmtime(d) > os.path.getmtime(out) for d in _paths(name)[1])
+    return any(os.path.getmtime(d) > os.path.getmtime(out) for d in lib_files(name))
 
 
 def build(force=False, verbose=False, names=None):
@@ -52,8 +61,8 @@ def build(force=False, verbose=False, names=None):
     for name in names or LIBS:
         if not force and not needs_build(name):
             continue
-        srcs, _ = _paths(name)
-        cmd = [HIPCC, *FLAGS, *LIBS[name][2], "-o", os.path.join(BUILD, name), *srcs]
+        srcs, flags = LIBS[name]
+        cmd = [HIPCC, *FLAGS, *flags, "-o", os.path.join(BUILD, name), *(os.path.join(CSRC, s) for s in srcs)]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -925,6 +925,36 @@ def check_supported(cfg):
         raise NotImplementedError("not on the accelerated path: " + lines)
 
 
+def fill_integrator_block(c, cfg, d, physics, n, actuator=None):
+    """The part of go1_config both step libraries read: the integrator / actuator block (sizes and timing, action
+    and clip scales, per-joint arrays, contact model, model block, actuator weights).  d: derived(cfg) or
+    vel_derived(cfg); physics: PHYSICS with the caller's overrides; actuator: flat weights in place of the data file."""
+    c.n_envs = int(n)
+    c.decimation = int(cfg.control.decimation)
+    c.n_internal = int(physics["n_internal"])
+    c.rand_interval = int(d["rand_interval"])
+    c.sim_dt = f32(cfg.sim.dt)
+    c.dt = f32(d["dt"])
+    c.action_scale = f32(cfg.control.action_scale)
+    c.hip_scale_reduction = f32(cfg.control.hip_scale_reduction)
+    c.clip_actions = f32(cfg.normalization.clip_actions)
+    c.clip_obs = f32(cfg.normalization.clip_observations)
+    c.max_episode_length = f32(d["max_episode_length"])
+    for i, nme in enumerate(L.DOF_NAMES):
+        c.default_dof_pos[i] = f32(cfg.init_state.default_joint_angles[nme])
+    soft = soft_dof_limits(getattr(cfg.rewards, "soft_dof_pos_limit", 1.0))
+    for i in range(12):
+        c.dof_pos_limits[2 * i], c.dof_pos_limits[2 * i + 1] = float(soft[i, 0]), float(soft[i, 1])
+        c.torque_limits[i] = f32(L.TORQUE_LIMIT)
+        lo, hi = L.JOINT_LIMITS[i % 3]
+        c.hard_limits[2 * i], c.hard_limits[2 * i + 1] = f32(lo), f32(hi)
+    set_contact_fields(c, cfg, physics)
+    for i, v in enumerate(M.model_block()):
+        c.model[i] = float(v)
+    for i, v in enumerate(actuator if actuator is not None else load_actuator()):
+        c.actuator[i] = float(v)
+
+
 def build_abi_config(cfg, n_envs=None, physics=None, actuator=None, hf_shape=(80, 40)):
     """go1_config for the C ABI from a (mutated) Cfg (raises NotImplementedError for any Cfg value
     the HIP step does not implement, see SUPPORTED)."""
@@ -934,7 +964,6 @@ def build_abi_config(cfg, n_envs=None, physics=None, actuator=None, hf_shape=(80
     c = abi.Go1Config()
     n = n_envs if n_envs is not None else cfg.env.num_envs
     plane = cfg.terrain.mesh_type == "plane"
-    c.n_envs = n
     c.terrain_kind = 0 if plane else 1
     c.camera_zero = int(bool(cfg.env.camera_zero))
     if plane and cfg.env.camera_zero:
@@ -989,18 +1018,8 @@ def build_abi_config(cfg, n_envs=None, physics=None, actuator=None, hf_shape=(80
     c.add_noise = int(bool(cfg.noise.add_noise))
     c.use_terminal_body_height = int(bool(cfg.rewards.use_terminal_body_height))
     c.custom_origins = 0 if plane else 1
-    c.decimation = cfg.control.decimation
-    c.n_internal = physics["n_internal"]
-    c.rand_interval = d["rand_interval"]
     c.hf_nx, c.hf_ny = hf_shape
-    c.sim_dt = f32(cfg.sim.dt)
-    c.dt = f32(d["dt"])
-    c.action_scale = f32(cfg.control.action_scale)
-    c.hip_scale_reduction = f32(cfg.control.hip_scale_reduction)
-    c.clip_actions = f32(cfg.normalization.clip_actions)
-    c.clip_obs = f32(cfg.normalization.clip_observations)
     c.horizontal_scale = f32(cfg.terrain.horizontal_scale)
-    c.max_episode_length = f32(d["max_episode_length"])
     c.terminal_body_height = f32(cfg.rewards.terminal_body_height)
     c.switch_dist = f32(cfg.commands.switch_dist)
     c.base_height_target = f32(cfg.rewards.base_height_target)
@@ -1054,15 +1073,6 @@ def build_abi_config(cfg, n_envs=None, physics=None, actuator=None, hf_shape=(80
     cm = cfg.commands
     c.traj_base_x, c.traj_base_y, c.traj_base_z = f32(cm.base_x), f32(cm.base_y), f32(cm.base_z)
     c.traj_roll, c.traj_pitch, c.traj_yaw = f32(cm.base_roll), f32(cm.base_pitch), 0.0
-    for i, nme in enumerate(L.DOF_NAMES):
-        c.default_dof_pos[i] = f32(cfg.init_state.default_joint_angles[nme])
-    soft = soft_dof_limits(getattr(cfg.rewards, "soft_dof_pos_limit", 1.0))
-    for i in range(12):
-        c.dof_pos_limits[2 * i] = float(soft[i, 0])
-        c.dof_pos_limits[2 * i + 1] = float(soft[i, 1])
-        c.torque_limits[i] = f32(L.TORQUE_LIMIT)
-        lo, hi = L.JOINT_LIMITS[i % 3]
-        c.hard_limits[2 * i], c.hard_limits[2 * i + 1] = f32(lo), f32(hi)
     g = scan_grid(cfg)
     c.scan_nx, c.scan_ny = g["nx"], g["ny"]
     for i, v in enumerate(g["x"]):
@@ -1074,12 +1084,7 @@ def build_abi_config(cfg, n_envs=None, physics=None, actuator=None, hf_shape=(80
             c.height_grid_x[i] = f32(v)
         for i, v in enumerate(g["y"]):
             c.height_grid_y[i] = f32(v)
-    set_contact_fields(c, cfg, physics)
-    for i, v in enumerate(M.model_block()):
-        c.model[i] = float(v)
-    w = actuator if actuator is not None else load_actuator()
-    for i, v in enumerate(w):
-        c.actuator[i] = float(v)
+    fill_integrator_block(c, cfg, d, physics, n, actuator)
     return c
 
 

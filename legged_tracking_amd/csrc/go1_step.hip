@@ -26,6 +26,8 @@
 #include "go1_device.h"
 #include "go1_step_shared.h"
 
+#define HOLD_N 23       // post-physics inputs parked in LDS across the step kernel's sub-step loop
+
 // =====================================================================
 //                          the fused step kernel
 // =====================================================================
@@ -1082,7 +1084,7 @@ int go1_create(const go1_config* cfg, go1_handle** out) {
   if (cfg->n_envs <= 0) return fail(GO1_E_ARG, "go1_create: n_envs must be > 0");
   if (cfg->decimation <= 0 || cfg->n_internal <= 0) return fail(GO1_E_ARG, "go1_create: decimation/n_internal");
   if (cfg->terrain_kind == 1 && (cfg->hf_nx < 2 || cfg->hf_ny < 2)) return fail(GO1_E_ARG, "go1_create: tile shape");
-  // the capsules' deepest-point search (go1_device.h seg_deepest) takes at most 3 grid lines per direction and 4 cell
+  // the capsules' deepest-point search (go1_contact.h seg_deepest) takes at most 3 grid lines per direction and 4 cell
   // diagonals per half link (0.1065 m): cells of at least 0.05 m
   if (cfg->terrain_kind == 1 && !(cfg->horizontal_scale >= 0.0499f))
     return fail(GO1_E_ARG, "go1_create: horizontal_scale < 0.05 m is not supported by the capsule contact search");

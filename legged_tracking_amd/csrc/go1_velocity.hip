@@ -3,7 +3,7 @@
 // One go1_vel_step = one VelocityTrackingEasyEnv.step + HistoryWrapper.step
 // (go1_gym/envs/base/legged_robot_velocity_tracking.py, bare :N below) in two launches:
 //   go1_vel_step_kernel: 4 x [actuator-net torques (:925-964) -> the native articulated-body integrator
-//     of go1_device.h (phys_substep, plane terrain)] -> post-physics (:108-154): kinematics, the gait
+//     of go1_phys.h (phys_substep, plane terrain)] -> post-physics (:108-154): kinematics, the gait
 //     clock (_step_contact_targets :844-923), DR (:714-717), terminations (:156-166), the CoRL reward
 //     terms and command sums (:281-318, go1_gym/envs/rewards/corl_rewards.py), reset_idx's state part
 //     (:168-257), observations (:320-509), the epilogue (:144-149) and the appended obs_history row.

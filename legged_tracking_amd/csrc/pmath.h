@@ -13,8 +13,7 @@
  * Compile with -ffp-contract=off: every a*b+c written below without fmaf must
  * stay two roundings.
  */
-#ifndef GO1_PMATH_H
-#define GO1_PMATH_H
+#pragma once
 #include <hip/hip_runtime.h>
 #define PM_FN __device__ __forceinline__
 
@@ -103,14 +102,10 @@ PM_FN float pm_atan2f(float y, float x) {
  * the fast form returns for an input clamped to +-2^30, so the input is clamped there
  * (between 2^24 and 2^25 |x| + 1 can round UP, and the quotient is then not +-1);
  * fma(q, x - x, q) returns q for finite x and NaN for inf / NaN, as IEEE does. */
-#ifndef GO1_FAST_SOFTSIGN
-#define GO1_FAST_SOFTSIGN 1
-#endif
 typedef float pm_f2 __attribute__((ext_vector_type(2)));
 #define PM_SOFTSIGN_LIM 1073741824.0f /* 2^30 */
 
 PM_FN float pm_softsign(float x) {
-#if GO1_FAST_SOFTSIGN
   const float xc = __builtin_amdgcn_fmed3f(x, -PM_SOFTSIGN_LIM, PM_SOFTSIGN_LIM);
   const float d = fabsf(xc) + 1.0f;
   const float r = __builtin_amdgcn_rcpf(d);
@@ -119,14 +114,10 @@ PM_FN float pm_softsign(float x) {
      sign of a zero quotient survives (-0 -> -0) */
   const float q = fmaf(-fmaf(q0, d, -xc), r, q0);
   return fmaf(q, x - x, q);
-#else
-  return x / (fabsf(x) + 1.0f);
-#endif
 }
 
 /* two softsigns in the halves of v_pk_mul / v_pk_fma (same roundings as pm_softsign) */
 PM_FN pm_f2 pm_softsign2(pm_f2 x) {
-#if GO1_FAST_SOFTSIGN
   /* one v_med3_f32 per half: fminf / fmaxf add a canonicalising v_max_f32 each (a NaN x
      becomes NaN again through the final fma with x - x, whatever the clamp returns) */
   const pm_f2 xc = {__builtin_amdgcn_fmed3f(x.x, -PM_SOFTSIGN_LIM, PM_SOFTSIGN_LIM),
@@ -136,9 +127,4 @@ PM_FN pm_f2 pm_softsign2(pm_f2 x) {
   const pm_f2 q0 = xc * r;
   const pm_f2 q = __builtin_elementwise_fma(-__builtin_elementwise_fma(q0, d, -xc), r, q0);
   return __builtin_elementwise_fma(q, x - x, q);
-#else
-  return pm_f2{x.x / (fabsf(x.x) + 1.0f), x.y / (fabsf(x.y) + 1.0f)};
-#endif
 }
-
-#endif

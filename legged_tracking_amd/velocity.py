@@ -13,7 +13,7 @@ configuration, common_step_counter with the global gravity schedule (:719-723, _
 when read).  No CPU fallback: without the HIP library or a GPU the constructor raises.
 
 Differences from the reference: physics is the native integrator (plane terrain, the
-contact model of go1_device.h), random draws are Philox keyed by (seed, global env, slot, step) instead
+contact model of go1_contact.h), random draws are Philox keyed by (seed, global env, slot, step) instead
 of torch's global generator and the curricula's RandomState, output tensors rotate through OUT_RING
 buffers, and the interval resample of a step runs ahead in the previous step's curriculum launch.
 """
@@ -121,33 +121,9 @@ def build_configs(cfg, n_envs=None, physics=None, env_id_offset=0, history_len=N
     f32 = CF.f32
     # ---- physics / actuator block (go1_config; trajectory-only fields stay zero)
     c = abi.Go1Config()
-    c.n_envs = n
+    CF.fill_integrator_block(c, cfg, d, physics, n)
     c.terrain_kind = 0
-    c.decimation = int(cfg.control.decimation)
-    c.n_internal = int(physics["n_internal"])
-    c.rand_interval = int(d["rand_interval"])
     c.env_id_offset = int(env_id_offset)
-    c.sim_dt = f32(cfg.sim.dt)
-    c.dt = f32(d["dt"])
-    c.action_scale = f32(cfg.control.action_scale)
-    c.hip_scale_reduction = f32(cfg.control.hip_scale_reduction)
-    c.clip_actions = f32(cfg.normalization.clip_actions)
-    c.clip_obs = f32(cfg.normalization.clip_observations)
-    c.max_episode_length = f32(d["max_episode_length"])
-    for i, nme in enumerate(L.DOF_NAMES):
-        c.default_dof_pos[i] = f32(cfg.init_state.default_joint_angles[nme])
-    soft = CF.soft_dof_limits(getattr(cfg.rewards, "soft_dof_pos_limit", 1.0))
-    for i in range(12):
-        c.dof_pos_limits[2 * i], c.dof_pos_limits[2 * i + 1] = float(soft[i, 0]), float(soft[i, 1])
-        c.torque_limits[i] = f32(L.TORQUE_LIMIT)
-        lo, hi = L.JOINT_LIMITS[i % 3]
-        c.hard_limits[2 * i], c.hard_limits[2 * i + 1] = f32(lo), f32(hi)
-    CF.set_contact_fields(c, cfg, physics)
-    from . import model as M
-    for i, x in enumerate(M.model_block()):
-        c.model[i] = float(x)
-    for i, x in enumerate(CF.load_actuator()):
-        c.actuator[i] = float(x)
     # ---- velocity block (go1_vel_config)
     v = VA.Go1VelConfig()
     v.n_envs = n

@@ -470,7 +470,7 @@ static void sphere_contact_im_cell(const TerrainView* T, const ContactParams* C,
     if (fn0 <= 0.0) continue;
     real fn = C->k * depth - (h * C->k + C->d) * vn;
     /* restitution: separating faster than the bounce threshold, the fraction e of the contact's damping
-       (h k + d) is handed back (go1_device.h restitute) */
+       (h k + d) is handed back (go1_contact.h restitute) */
     if (C->e > 0.0 && vn > C->vb) fn += C->e * (h * C->k + C->d) * vn;
     real vt[3] = {pv[0] - vn * n[0], pv[1] - vn * n[1], pv[2] - vn * n[2]};
     real vtn = sqrt(vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
@@ -565,7 +565,7 @@ static void sphere_contact(const TerrainView* T, const ContactParams* C, const r
  * flat is carried at both ends). */
 
 /* The deepest point of the segment A -> B (world) of a capsule of radius r against the floor and ceiling meshes
- * (go1_device.h seg_deepest2 is the f32 restatement): the t in [0, 1] that maximises the vertical gap of either layer,
+ * (go1_contact.h seg_deepest2 is the f32 restatement): the t in [0, 1] that maximises the vertical gap of either layer,
  * floor h_f(x, y) + r - z and ceiling z + r - h_c(x, y).  Both meshes are triangles over the grid (tri_query), so
  * along the segment the gaps are piecewise linear in t and their maximum lies at an end or where the segment's (x, y)
  * projection crosses a mesh edge: a grid line u = k, v = k or a cell diagonal u - v = k.  The candidates are exactly
@@ -704,7 +704,7 @@ void go1o_seg_closest(const double* P0, const double* P1, const double* Q0, cons
  * fraction in f32 and f64 alike).  Outside the box the distance |q+| (q_i = |c_i| - th_i) has the derivative's sign
  * of sum_i q+_i sgn(c_i) d_i; inside, max_i q_i has sgn(c_k) d_k for the deepest axis k (the lowest on ties).  Round
  * 6's first cut ran a golden-section search on the distance itself (32 evaluations with a square root each), the
- * slowest waves' largest section.  go1_device.h seg_box_t is the f32 restatement. */
+ * slowest waves' largest section.  go1_selfcol.h seg_box_t is the f32 restatement. */
 #define SEG_BISECT 20
 #define BOX_Q 1.0e-4
 static long box_quant(real d) { return (long)floor(fmin(fmax(d, -1.0), 1.0) / BOX_Q); }
@@ -759,7 +759,7 @@ static void point_force(real Rb[3][3], const real* lp, const real* F, real* fs) 
 }
 
 /* Self-collision (asset.self_collisions == 0, go1_crawling.py:44: Isaac Gym collides every pair of bodies that
- * no joint connects; go1_device.h self_narrow): the primitives 4 leg + k of the legs (k: 0 thigh capsule, 1 hip
+ * no joint connects; go1_selfcol.h self_narrow): the primitives 4 leg + k of the legs (k: 0 thigh capsule, 1 hip
  * capsule, 2 calf capsule, 3 foot sphere; the collision geometry above); pairs: every primitive of leg la against
  * every primitive of leg lb (la < lb, 16 per leg pair), within a leg the links two joints apart (hip capsule vs calf
  * capsule and foot, thigh capsule vs foot: SELF_SAME_A / _B), and the thigh / calf capsules and the foot against
@@ -826,7 +826,7 @@ static void self_box_force(const real* pa, const real* va, real r, real R[3][3],
   for (int i = 0; i < 3; ++i) { wb[i] += tq[i]; wb[3 + i] += fb[i]; }
 }
 
-/* The trunk box's faces against the heightfields (go1_device.h face_scan / face_force; go1.urdf:53-58,
+/* The trunk box's faces against the heightfields (go1_contact.h face_scan / face_force; go1.urdf:53-58,
  * tunnel_fn.py:99-163): once per control step, per face the grid vertex inside its footprint nearest to (or deepest
  * in) the face -- the floor against the bottom face, the ceiling against the top -- among the 10 x 10 vertices around
  * the trunk centre (offsets -4 .. +5 on both axes: they cover the footprint's +-0.166 m at any yaw, whatever the

@@ -1,5 +1,5 @@
 """Numpy kinematics of the 16 self-collision primitives in the trunk frame (shares nothing with the kernel or the
-oracle): the self-collision tests' pose pools, the fold-gate soundness check (go1_device.h self_broad) and the
+oracle): the self-collision tests' pose pools, the fold-gate soundness check (go1_selfcol.h self_broad) and the
 coverage properties of the capsule geometry (tests/test_self_collision.py).
 
 Primitive 4 l + k of leg l (k: 0 thigh capsule, 1 hip capsule, 2 calf capsule, 3 foot sphere; model.py and

@@ -12,7 +12,7 @@ one a case the sphere chains failed (asserted alongside as documentation):
   * a floor vertex raised under any point of the thigh or calf -- the middle of the calf between the old spheres
     included -- meets a force on that link (the sphere chain missed the vertex under the middle of the calf);
   * a foot overlapping another leg's thigh or calf capsule anywhere meets a force on both bodies.
-The GPU kernel (go1_device.h seg_deepest / self_narrow) is checked against the same oracle in
+The GPU kernel (go1_contact.h seg_deepest / go1_selfcol.h self_narrow) is checked against the same oracle in
 tests/test_gpu_self_collision.py and tests/test_gpu_parity.py.
 """
 import numpy as np

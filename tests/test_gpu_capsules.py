@@ -1,5 +1,5 @@
 """The capsule links against the triangle-mesh floor on the MI355X (round 6): the HIP step's deepest
-point of a link segment (go1_device.h seg_deepest: ends, grid-line and diagonal crossings) against the f64 oracle, on
+point of a link segment (go1_contact.h seg_deepest: ends, grid-line and diagonal crossings) against the f64 oracle, on
 the case the round-3..5 sphere chains failed -- a single floor vertex raised under any point along the thigh or calf.
 
 32 envs, one sub-terrain tile each (single_path layout, README configuration at decimation 1, so the reported

@@ -265,7 +265,7 @@ def test_foot_overlapping_another_legs_link_meets_a_force():
 
 def test_trunk_face_contacts_step_vs_oracle():
     """the trunk's top face against ceiling apexes and its bottom face against a floor ridge that
-    lie between the box corners (go1_device.h face_scan / face_force against oracle/go1_oracle.c).  Every tile gets
+    lie between the box corners (go1_contact.h face_scan / face_force against oracle/go1_oracle.c).  Every tile gets
     a flat floor and ceiling with three downward ceiling spikes and a raised floor ridge under the trunk; every
     env's trunk sits over them, level to within 0.1 rad and yawed up to 0.5 rad, at heights that put the spikes and
     the ridge 0-15 mm into its faces.  README configuration (decimation 4, the specialised kernel), three control

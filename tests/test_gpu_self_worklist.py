@@ -1,4 +1,4 @@
-"""The self-collision narrow phase's work list on crafted states (go1_device.h self_narrow), 16 envs = four waves.
+"""The self-collision narrow phase's work list on crafted states (go1_selfcol.h self_narrow), 16 envs = four waves.
 
 The narrow phase takes its partner boxes from registers, skips the pair spring in a wave where no pair touches, and
 writes the primitives' velocity records only in a wave and a sim step where a pair touches.  Crafted joint states

@@ -1,7 +1,7 @@
 """The contact choices the step kernel holds for a control step, against choosing them every sim step (VERDICT r05
 #4: "move the trunk-face vertex selection to every sim step, or add a test bounding the error of holding it").
 
-The kernel (go1_device.h phys_substep) makes two discrete choices once per control step, on its first sim step, and
+The kernel (go1_phys.h phys_substep) makes two discrete choices once per control step, on its first sim step, and
 holds them for the other decimation - 1 = 3: the deepest point t of every capsule segment against the floor /
 ceiling meshes (seg_deepest; the point then moves with its link, and its triangle is re-located under it) and the
 trunk faces' two deepest terrain vertices (face_scan; the penalty force acts at them every sim step, face_force).

@@ -3,7 +3,7 @@ go1.urdf:106-111 / :229-234, as capsules, legged_robot_trajectory_tracking_confi
 
 The native model carries each hip capsule as the two ends of its segment (model.py HIP_CAPSULE_*),
 spheres of the capsule's radius on the hip link, in the f64 oracle (oracle/go1_oracle.c phys_substep
-j == 0) and in the HIP integrator (csrc/go1_device.h hip_contact).  Scenario: the trunk rolled 34-46
+j == 0) and in the HIP integrator (csrc/go1_phys.h phys_substep, role 1).  Scenario: the trunk rolled 34-46
 degrees to the left with the legs folded up, lowered until the left hips' outer capsule ends press
 2-10 mm into the plane, so the hips are the only bodies in contact.
 

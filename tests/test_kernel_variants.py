@@ -1,6 +1,7 @@
 """Every diagnostic build of the step kernels still compiles (no GPU needed).
 
-go1_step.hip (with the device code it shares with the velocity step, go1_device.h and go1_step_shared.h) keeps two kinds of compile-time switches, both measurement instrumentation, never
+go1_step.hip (with the device code it shares with the velocity step: go1_device.h, the part headers it includes and
+go1_step_shared.h) keeps two kinds of compile-time switches, both measurement instrumentation, never
 shipped: the ablation builds of tools/abl_kernel.sh (GO1_ABL_*: a section of the kernel compiled
 out, to price it in situ) and the timing / accounting builds (GO1_STAMPS: s_memtime stamps for
 tools/stamps.py; GO1_ISA_MARKS: section markers for tools/isa_sections.py).  Variants that were
@@ -16,10 +17,13 @@ from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
+from legged_tracking_amd import build as B
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "legged_tracking_amd", "csrc")
 SRC = os.path.join(CSRC, "go1_step.hip")
-SCANNED = [SRC, os.path.join(CSRC, "go1_device.h"), os.path.join(CSRC, "go1_step_shared.h")]
+# go1_step.hip and every csrc header it reaches: go1_device.h, its parts, go1_step_shared.h, ...
+SCANNED = [f for f in B.include_closure([SRC]) if os.path.dirname(f) == CSRC]
 VEL_SRC = os.path.join(CSRC, "go1_velocity.hip")
 ROLLOUT_SRC = os.path.join(CSRC, "rollout.hip")
 PPO_SRC = os.path.join(CSRC, "ppo_update.hip")
@@ -46,6 +50,23 @@ def test_only_diagnostic_switches_remain():
     stray = {c for c in conds if c.startswith(("GO1_", "PPO_")) and c not in allowed}
     assert {"GO1_POLICY_STAMPS", "PPO_STAMPS"} <= conds and not stray, \
         f"variant switches in rollout.hip / ppo_update.hip: {sorted(stray)}"
+
+
+@pytest.mark.parametrize("name", B.LIBS)
+def test_every_include_is_watched_by_needs_build(name):
+    """A library is rebuilt when any file it is made of changes: every quoted include reachable from its sources
+    exists, lies in csrc/ or include/, and is in the set needs_build compares with the library (build.lib_files).
+    The scan here is the test's own, file by file."""
+    watched = set(B.lib_files(name))
+    assert {os.path.join(CSRC, s) for s in B.LIBS[name][0]} <= watched
+    for f in sorted(watched):
+        assert os.path.isfile(f) and os.path.dirname(f) in (CSRC, INC), f
+        for line in open(f):
+            m = re.match(r'\s*#\s*include\s+"([^"]+)"', line)
+            if m:
+                inc = os.path.normpath(os.path.join(os.path.dirname(f), m.group(1)))
+                assert os.path.isfile(inc), f"{f} includes a missing file: {m.group(1)}"
+                assert inc in watched, f"{name} is not rebuilt when {inc} changes (included by {f})"
 
 
 @pytest.mark.skipif(not shutil.which(HIPCC) and not os.path.exists(HIPCC), reason="hipcc not available")

@@ -74,11 +74,11 @@ def test_argument_errors_are_reported_not_thrown():
 def test_render_library_keeps_the_step_libraries_build_as_it_was():
     """The ray caster is a library of its own with the plain flags; it shares no source or dependency with the
     step libraries."""
-    srcs, deps, flags = B.LIBS["libgo1_render.so"]
+    srcs, flags = B.LIBS["libgo1_render.so"]
     assert srcs == ["go1_render.hip"] and flags == []
     other = set()
-    for name, (s, d, _) in B.LIBS.items():
+    for name in B.LIBS:
         if name != "libgo1_render.so":
-            other |= {os.path.basename(x) for x in s + d}
-    assert not ({os.path.basename(x) for x in srcs + deps} & other)
+            other |= {os.path.basename(x) for x in B.lib_files(name)}
+    assert not ({os.path.basename(x) for x in B.lib_files("libgo1_render.so")} & other)
     assert "go1_model_consts.h" not in open(os.path.join(B.HERE, "csrc", "go1_render.hip")).read()

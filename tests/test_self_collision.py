@@ -175,7 +175,7 @@ def test_restitution_drop_apex_is_pinned():
 
 
 def test_fold_gate_is_sound():
-    """go1_device.h self_broad tests a leg's same-leg pairs and its primitives against the trunk box only while one of
+    """go1_selfcol.h self_broad tests a leg's same-leg pairs and its primitives against the trunk box only while one of
     its joints is more than 0.1 rad past its URDF range (the oracle always tests them).  Sound if none of those
     pairs can touch inside the band: on a grid of step h the clearance stays above what a grid cell can close
     (per joint: the lever arm of the farthest collision point about its axis x h / 2).  The same-leg geometry does

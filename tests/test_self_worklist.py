@@ -1,4 +1,4 @@
-"""The self-collision work list is conservative (CPU; go1_device.h self_broad / self_narrow restated in numpy).
+"""The self-collision work list is conservative (CPU; go1_selfcol.h self_broad / self_narrow restated in numpy).
 
 The step kernel evaluates a primitive pair only if it is on the lane's work list:
   * cross-leg pairs: the two legs' trunk-frame boxes overlap (self_broad: the thigh joint, the knee .. foot span grown

@@ -1,6 +1,6 @@
 """The trunk box's faces against the heightfields: the deepest grid vertex of the ceiling
 inside the top face's footprint and of the floor inside the bottom face's, chosen once per control step, carry a
-penalty force every sim step (oracle/go1_oracle.c face_scan / face_force; go1_device.h the same on the GPU).
+penalty force every sim step (oracle/go1_oracle.c face_scan / face_force; go1_contact.h the same on the GPU).
 
 Reference scene: the trunk's collision box is 0.3762 x 0.0935 x 0.114 (resources/robots/go1/urdf/go1.urdf:53-58) and
 PhysX collides it with the tunnel's trimesh (legged_robot_trajectory_tracking.py:1450-1480), whose ceiling is made

@@ -1,6 +1,6 @@
 """CPU study: how loose the self-collision broad phase is on the bench workload (single_path, N(0, 1) actions).
 Steps the f64 oracle, and after every control step compares, per env and per leg pair, the trunk-frame AABB
-overlap of go1_device.h self_broad (thigh joint / knee / foot grown by the largest link radius, plus the hip
+overlap of go1_selfcol.h self_broad (thigh joint / knee / foot grown by the largest link radius, plus the hip
 capsule) with exact sphere overlaps and with tighter candidate tests.  Prints rates per env and per 4-env wave."""
 import os
 import sys

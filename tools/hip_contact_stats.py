@@ -1,6 +1,6 @@
 """How often the hip capsules touch in the bench workload (bench.py make_env: README single_path config,
 4096 envs, N(0, 1) actions): the fraction of envs with a hip contact force, and of 4-env waves in which
-the step kernel's hip-contact branch runs (csrc/go1_device.h hip_contact).  GPU diagnostic:
+the step kernel's hip-contact branch runs (csrc/go1_phys.h phys_substep, role 1).  GPU diagnostic:
   python tools/hip_contact_stats.py [steps]"""
 import json
 import os

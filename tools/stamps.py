@@ -59,8 +59,10 @@ def main():
     g.close()
 
     name = {}
-    for f in ("go1_step.hip", "go1_device.h", "go1_step_shared.h"):  # (a line number marked in several files names them all)
-        src = open(os.path.join(ROOT, "legged_tracking_amd", "csrc", f)).read().splitlines()
+    from legged_tracking_amd import build as B
+    # go1_step.hip and the headers it includes (a line number marked in several files names them all)
+    for f in B.include_closure([os.path.join(B.CSRC, "go1_step.hip")]):
+        src = open(f).read().splitlines()
         for i, l in enumerate(src):
             m = re.search(r"MARK\((\w+)\)", l)
             if m:
