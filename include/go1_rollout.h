@@ -98,6 +98,41 @@ typedef struct go1_policy_args {
   int64_t hist_ld;             /* row stride of obs_history in floats (0: hist_dim; >= hist_dim) */
 } go1_policy_args;
 
+/* Height-map encoder of go1_gym_learn/ppo_cse_cnn (actor_critic.py:27-62, 180-198; csrc/encoder.hip): from the
+ * LAST frame of every history row, policy_input = [scalars | scalars | embedding of the frame's height map], the
+ * row go1_policy_forward then takes as its "history" (hist_dim = 2 n_scalar + n_embed).  A frame is n_scalar
+ * scalars followed by the (2, map_x, map_y) map.  Same 3xF16 split products and range guard as the policy kernel.
+ *   GO1_ENC_MLP: Linear(2 X Y -> n_feat) ELU Linear(n_feat -> n_embed) ELU
+ *   GO1_ENC_CNN: Conv3x3(2 -> 16) ReLU MaxPool2 Conv3x3(16 -> 32) ReLU MaxPool2 Flatten Linear(n_feat -> n_embed),
+ *                n_feat = 32 (X / 2 / 2) (Y / 2 / 2) with floor pooling, zero padding at the true map border
+ * layers: MLP (linear 1, linear 2); CNN (conv 1, conv 2, linear).  A conv's weights are packed as the linear
+ * layer [oc][ic * 9 + ky * 3 + kx] (K = 9 ic padded to 32); wf is the tensor as torch keeps it. */
+#define GO1_ENCODER_LAYERS 3
+#define GO1_ENC_MLP 0
+#define GO1_ENC_CNN 1
+#define GO1_ENC_MAX_EMBED 512
+typedef struct go1_encoder_args {
+  const float* obs_history;  /* (n, >= frame_off + num_obs), rows hist_ld floats apart */
+  int64_t hist_ld;           /* row stride of obs_history in floats, >= frame_off + num_obs */
+  int64_t frame_off;         /* column of the last frame: (H - 1) * num_obs */
+  int32_t num_obs;           /* frame width = n_scalar + 2 * map_x * map_y */
+  int32_t n_scalar;
+  int32_t map_x, map_y;      /* 1 .. GO1_MAX_SCAN_X (64), 1 .. GO1_MAX_SCAN_Y (32) of go1_mi355x.h */
+  int32_t mode;              /* GO1_ENC_MLP / GO1_ENC_CNN */
+  int32_t n_embed;           /* E, 1 .. GO1_ENC_MAX_EMBED */
+  int32_t n_feat;            /* K of the last linear layer: the MLP's hidden width, the CNN's flattened features */
+  int32_t n_envs;
+  go1_policy_layer layers[GO1_ENCODER_LAYERS];
+  float* scratch;            /* (n, n_feat) f32: the MLP's hidden activations / the CNN's pooled features */
+  float* policy_input;       /* (n, 2 n_scalar + n_embed), rows out_ld floats apart; rows >= n_envs are not written */
+  int64_t out_ld;            /* >= 2 n_scalar + n_embed */
+  int32_t* overflow;         /* optional: += workgroups that recomputed in f32 (the range guard) */
+} go1_encoder_args;
+
+int go1_heightmap_encode(const go1_encoder_args* args, void* stream);
+/* sizeof(go1_policy_layer), sizeof(go1_encoder_args) */
+void go1_encoder_abi_sizes(int64_t out[2]);
+
 int go1_rollout_abi_version(void);
 /* sizeof(go1_transition), sizeof(go1_policy_layer), sizeof(go1_policy_args): lets a foreign binding verify
  * its struct mirrors. */

@@ -11,6 +11,7 @@ resolve to this package:
   go1_gym.envs.go1.trajectory_tracking.TrajectoryTrackingEnv -> env.TrajectoryTrackingEnv
   go1_gym.envs.wrappers.history_wrapper.HistoryWrapper -> env.HistoryWrapper
   go1_gym_learn.ppo_cse{,.actor_critic,.ppo}          -> rollout (Runner, RunnerArgs, AC_Args, PPO_Args)
+  go1_gym_learn.ppo_cse_cnn{,.actor_critic,.ppo}      -> rollout_cnn (train.py's default, without --old_ppo)
   wandb                                               -> no-op stand-in when wandb is not installed
 and, for scripts/train_velocity_tracking.py (BASELINE configs[1]):
   go1_gym.envs.base.legged_robot_velocity_tracking_config.Cfg -> velocity_config.make_vel_cfg()
@@ -54,12 +55,15 @@ def install(root_dir=None):
             super().__init__(sim_device, headless, num_envs, prone, deploy, cfg, eval_cfg, initial_dynamics_dict,
                              physics_engine)
 
-    class Runner(R.Runner):
+    class _Capped:  # GO1_MAX_ITERATIONS caps learn()'s iterations
         def learn(self, num_learning_iterations, *a, **k):
             cap = os.environ.get("GO1_MAX_ITERATIONS")
             if cap:
                 num_learning_iterations = min(num_learning_iterations, int(cap))
             return super().learn(num_learning_iterations, *a, **k)
+
+    class Runner(_Capped, R.Runner):
+        pass
 
     from . import velocity as VEL, velocity_config as VC
 
@@ -104,6 +108,17 @@ def install(root_dir=None):
     _module("go1_gym_learn.ppo_cse.actor_critic", **ppo)
     _module("go1_gym_learn.ppo_cse.ppo", **ppo)
     _module("go1_gym_learn.ppo_cse.rollout_storage", **ppo)
+    from . import rollout_cnn as RC
+
+    class RunnerCNN(_Capped, RC.Runner):
+        pass
+
+    cnn = dict(ppo, Runner=RunnerCNN, ActorCritic=RC.ActorCritic, AC_Args=RC.AC_Args,
+               HeightMapEncoder=RC.HeightMapEncoder)
+    _module("go1_gym_learn.ppo_cse_cnn", **cnn)
+    _module("go1_gym_learn.ppo_cse_cnn.actor_critic", **cnn)
+    _module("go1_gym_learn.ppo_cse_cnn.ppo", **cnn)
+    _module("go1_gym_learn.ppo_cse_cnn.rollout_storage", **cnn)
     try:
         import wandb  # noqa: F401
     except ImportError:

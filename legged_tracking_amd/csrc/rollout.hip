@@ -20,10 +20,9 @@
 #include <string>
 
 #include "../../include/go1_rollout.h"
+#include "split_mfma.h"
 
 namespace {
-
-typedef float f4_t __attribute__((ext_vector_type(4)));
 
 // Philox4x32-10 (Salmon et al. 2011), as in the env step kernel
 __device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t k1) {
@@ -247,10 +246,6 @@ constexpr int PIN = 288;  // 261 / 263 inputs padded to a multiple of 32
 constexpr int PW = 16;    // waves per workgroup (four per SIMD)
 
 typedef go1_policy_layer PolicyLayer;  // w packed [n/16][k/32][64 lanes][8 hi + 8 lo halves], b [n padded to 16]
-typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 h16_t __attribute__((ext_vector_type(16)));
-typedef float f8_t __attribute__((ext_vector_type(8)));  // one lane's weight fragment (32 bytes)
 
 // split activation planes in LDS: element (k, env c) at [k / 8][c][k % 8] of hi, and of lo
 struct ActV {
@@ -263,11 +258,6 @@ struct Act {
   h8_t lo[K / 8][16];
   __device__ ActV v() { return ActV{&hi[0][0], &lo[0][0]}; }
 };
-
-// ELU's negative branch through the hardware exponential (v_exp_f32): exp(x) - 1 loses relative accuracy
-// only where |x| is tiny, where its absolute error stays ~6e-8 (the outputs are checked at 2e-5 of their
-// scale against f64); expm1f's range reduction cost ~25 instructions per value on the workgroups' tails
-__device__ __forceinline__ float elu(float x) { return x > 0.0f ? x : __expf(x) - 1.0f; }
 
 // Normal(0, 1) draws of actions 4 q .. 4 q + 3 of global env gid: one Philox4x32-10 block keyed by
 // (env, action group, step), two Box-Muller pairs on the hardware log2 / sqrt / sin / cos (v_sin / v_cos
@@ -285,12 +275,6 @@ __device__ __forceinline__ void normal4(uint32_t gid, int q, uint64_t step, uint
   }
 }
 
-// Range guard of the split: f16(x) overflows for |x| >= 65520 (and a NaN / inf input has no split), so a
-// value outside (-65504, 65504) sets the workgroup's flag; the workgroup then recomputes its envs in
-// f32 from the unsplit weights at its end (policy_fallback).  One compare per stored value.
-__device__ __forceinline__ void ovf_check(float v, int* ovf) {
-  if (!(fabsf(v) < 65504.0f)) *ovf = 1;
-}
 // four consecutive features 4 kq .. 4 kq + 3 of env c, split into the two planes
 __device__ __forceinline__ void act_store4(ActV d, int kq, int c, f4_t v, int* ovf) {
   h4_t h, l;
@@ -308,16 +292,6 @@ __device__ __forceinline__ void act_store1(ActV d, int k, int c, float v, int* o
   const _Float16 h = (_Float16)v;
   reinterpret_cast<_Float16*>(d.hi)[((k >> 3) * 16 + c) * 8 + (k & 7)] = h;
   reinterpret_cast<_Float16*>(d.lo)[((k >> 3) * 16 + c) * 8 + (k & 7)] = (_Float16)(v - (float)h);
-}
-
-// acc += W x over one 32-deep K group: w = (8 hi, 8 lo) halves of the lane's A fragment
-__device__ __forceinline__ f4_t mfma3(f8_t w, h8_t xh, h8_t xl, f4_t acc) {
-  const h16_t wv = __builtin_bit_cast(h16_t, w);
-  const h8_t wh = __builtin_shufflevector(wv, wv, 0, 1, 2, 3, 4, 5, 6, 7);
-  const h8_t wl = __builtin_shufflevector(wv, wv, 8, 9, 10, 11, 12, 13, 14, 15);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl, acc, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh, acc, 0, 0, 0);
 }
 
 template <int NT, int NL>
@@ -1172,6 +1146,9 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restri
   for (; p < P; ++p) acc += partial[(int64_t)p * C + c];
   out[c] = acc;
 }
+
+// the library's error record for its other sources (encoder.hip)
+int go1_rt_fail(int code, const std::string& m) { return fail(code, m); }
 
 extern "C" {
 

@@ -10,6 +10,9 @@ GO1_ROLLOUT_ABI_VERSION = 1
 GO1_PPO_ABI_VERSION = 1
 GO1_POLICY_LAYERS = 11
 GO1_PPO_AUX = 8
+GO1_ENCODER_LAYERS = 3
+GO1_ENC_MLP, GO1_ENC_CNN = 0, 1
+GO1_ENC_MAX_EMBED = 512
 
 P = C.c_void_p
 I32 = C.c_int32
@@ -37,6 +40,13 @@ class PolicyArgs(C.Structure):  # go1_policy_args
                 ("layers", PolicyLayer * GO1_POLICY_LAYERS), ("hist_ld", I64)]
 
 
+class EncoderArgs(C.Structure):  # go1_encoder_args
+    _fields_ = [("obs_history", P), ("hist_ld", I64), ("frame_off", I64), ("num_obs", I32), ("n_scalar", I32),
+                ("map_x", I32), ("map_y", I32), ("mode", I32), ("n_embed", I32), ("n_feat", I32), ("n_envs", I32),
+                ("layers", PolicyLayer * GO1_ENCODER_LAYERS), ("scratch", P), ("policy_input", P), ("out_ld", I64),
+                ("overflow", P)]
+
+
 class PPODims(C.Structure):  # go1_ppo_dims
     _fields_ = [("hist", I32), ("priv", I32), ("actions", I32), ("mb", I32), ("rows", I64)]
 
@@ -56,6 +66,8 @@ _PP = C.POINTER
 ROLLOUT_ARGTYPES = {
     "go1_rollout_abi_sizes": [_PP(I64)],
     "go1_policy_forward": [_PP(PolicyArgs), P],
+    "go1_encoder_abi_sizes": [_PP(I64)],
+    "go1_heightmap_encode": [_PP(EncoderArgs), P],
     "go1_record_transition": [_PP(Transition), I32, C.c_float, P],
     "go1_gae": [P] * 7 + [I32, I32, C.c_float, C.c_float, P],
     "go1_adv_normalize": [P, P, C.c_double, I64, P],

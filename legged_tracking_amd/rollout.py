@@ -102,7 +102,11 @@ def _pack_linear(lin):
     [n/16][k/32][lane = 16 q + m][hi r = 0..7, lo r = 0..7] of W[16 t + m][32 g + 8 q + r]: lane
     (m, q) of output tile t reads one record per 32-deep K group g -- its A fragments of
     v_mfma_f32_16x16x32_f16 (row m, k = 8 q .. 8 q + 7) for both halves of the split."""
-    W, b = lin.weight.detach().float(), lin.bias.detach().float()
+    return _pack_matrix(lin.weight.detach().float(), lin.bias.detach().float())
+
+
+def _pack_matrix(W, b):
+    """_pack_linear for a weight matrix (n, k) and its bias (rollout_cnn packs a convolution's filters this way)."""
     n, k = W.shape
     npad, kpad = -(-n // 16) * 16, -(-k // 32) * 32
     Wp = torch.zeros(npad, kpad, device=W.device, dtype=torch.float32)
@@ -260,7 +264,10 @@ class HipRolloutKernels:
             native.raw_stream(st.rewards.device)))
 
     def policy(self, ac):
-        return FusedPolicy(ac) if FusedPolicy.supported(ac) else None
+        if FusedPolicy.supported(ac):
+            return FusedPolicy(ac)
+        from . import rollout_cnn  # the height-map encoder module (imports this one)
+        return rollout_cnn.fused_policy(ac)
 
     def normalize(self, st, count):
         native.check(self.lib, self.lib.go1_adv_normalize(st.advantages.data_ptr(), st.adv_stats.data_ptr(),
@@ -413,6 +420,10 @@ class ActorCritic(nn.Module):
     def evaluate_train(self, observation_history, privileged_observations):
         return _mlp_train(self.critic_body, torch.cat((observation_history, privileged_observations), dim=-1))
 
+    def adaptation_pred_train(self, observation_history):
+        """The adaptation step's prediction (ppo.py:170)."""
+        return _mlp_train(self.adaptation_module, observation_history)
+
 
 # ----------------------------------------------------------------------------- storage
 class RolloutStorage:
@@ -536,7 +547,8 @@ class PPO:
         # captured once into a HIP graph and replayed for every later mini-batch (GO1_PPO_GRAPH=0: eager):
         # it is ~150 small launches whose host issue left the GPU idle between them.  One rank only (the
         # gradient all-reduce stays eager).
-        self._graph_on = self._dev_lr and os.environ.get("GO1_PPO_GRAPH", "1") != "0"
+        self._graph_on = (self._dev_lr and os.environ.get("GO1_PPO_GRAPH", "1") != "0"
+                          and getattr(actor_critic, "graph_capture", True))
         self._graph = self._graph_key = None
         self._graph_warm = 0
         self._graph_idx = self._graph_acc = self._graph_draw = None  # static buffers of the captured step
@@ -731,7 +743,7 @@ class PPO:
         acc[1] += surrogate_loss.detach()
         num_train = int(priv_b.shape[0] // 5 * 4)
         for _ in range(A.num_adaptation_module_substeps):
-            pred = _mlp_train(ac.adaptation_module, hist_b)
+            pred = ac.adaptation_pred_train(hist_b)
             with torch.no_grad():
                 target = priv_b
             # every column (ppo.py:193: linspace(0, w - 1, w) as an index), or column 0
@@ -896,6 +908,8 @@ class Runner:
     iteration, GAE, PPO update, checkpoints (ac_weights.pt + TorchScript adaptation
     module and actor body, the formats scripts/eval.py and the deploy stack read)."""
 
+    actor_critic_class = ActorCritic  # rollout_cnn.Runner: the height-map encoder module
+
     def __init__(self, env, device="cpu", runner_args=RunnerArgs, ac_args=AC_Args, log_wandb=False, kernels=None,
                  save_dir=None):
         self.device = device
@@ -903,7 +917,8 @@ class Runner:
         self.runner_args = runner_args
         self.log_wandb = log_wandb
         self.save_dir = save_dir
-        ac = ActorCritic(env.num_obs, env.num_privileged_obs, env.num_obs_history, env.num_actions).to(device)
+        ac = self.actor_critic_class(env.num_obs, env.num_privileged_obs, env.num_obs_history,
+                                     env.num_actions).to(device)
         if runner_args.resume:
             ac.load_state_dict(torch.load(runner_args.resume, map_location=device, weights_only=True))
         self.alg = PPO(ac, device=device, kernels=kernels)
