@@ -454,13 +454,27 @@ __device__ __forceinline__ void face_scan(const Terr& T, const float* R, const f
   const int ci = (int)floorf(fminf(fmaxf(pos[0] * ihs, -16000.0f), 16000.0f));
   const int cj = (int)floorf(fminf(fmaxf(pos[1] * ihs, -16000.0f), 16000.0f));
   int key[2] = {-1, -1};
+  // the lane's seven window vertices: every read issued, then one wait (read and used in one loop, each read was
+  // waited for by itself: seven LDS round trips in a row)
+  constexpr int NU = (FACE_W * FACE_W + 15) / 16;
+  static_assert(NU == 7, "the operand list below");
+  float2 hw[NU];
 #pragma unroll
-  for (int u = 0; u < (FACE_W * FACE_W + 15) / 16; ++u) {
+  for (int u = 0; u < NU; ++u) {
+    const int v = sub16 + 16 * u;
+    const int li = ci + v % FACE_W - 4 - T.pi0, lj = cj + v / FACE_W - 4 - T.pj0;
+    hw[u] = T.patch[min(max(li, 0), PSZX - 1) * PSZY + min(max(lj, 0), PSZY - 1)];
+  }
+  asm volatile("" : "+v"(hw[0].x), "+v"(hw[0].y), "+v"(hw[1].x), "+v"(hw[1].y), "+v"(hw[2].x), "+v"(hw[2].y),
+                    "+v"(hw[3].x), "+v"(hw[3].y), "+v"(hw[4].x), "+v"(hw[4].y), "+v"(hw[5].x), "+v"(hw[5].y),
+                    "+v"(hw[6].x), "+v"(hw[6].y));
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
     const int v = sub16 + 16 * u;
     const int i = ci + v % FACE_W - 4, j = cj + v / FACE_W - 4;
     const int li = i - T.pi0, lj = j - T.pj0;
     const bool inp = (v < FACE_W * FACE_W) & (li >= 0) & (li < PSZX) & (lj >= 0) & (lj < PSZY);
-    const float2 hv = T.patch[min(max(li, 0), PSZX - 1) * PSZY + min(max(lj, 0), PSZY - 1)];
+    const float2 hv = hw[u];
     const float dx = (float)i * T.hs - pos[0], dy = (float)j * T.hs - pos[1];
     const f2 dz = f2{hv.x, hv.y} - pos[2];
     const f2 cx = (R[0] * dx + R[3] * dy) + R[6] * dz, cy = (R[1] * dx + R[4] * dy) + R[7] * dz,

@@ -27,6 +27,38 @@ struct Phys {
   float q[3], qd[3];                   // this lane's leg
 };
 
+// A wave-uniform value pinned in an SGPR: opaque from here on, so the compiler keeps it (in the SGPR, or spilled to
+// a VGPR lane and read back with v_readlane, no memory wait) where it would otherwise re-load a config field.
+template <class V>
+__device__ __forceinline__ void pin_s(V& v) {
+  static_assert(sizeof(V) == 4, "one SGPR");
+  // (readfirstlane: a value the VALU computed, such as the step length's division, lives in a VGPR)
+  int s = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v));
+  asm volatile("" : "+s"(s));
+  v = __builtin_bit_cast(V, s);
+}
+// The config scalars every integrator step reads, read once per launch (sub_consts) in front of the decimation
+// loop.  They stay run-time values: as compile-time constants they would move the integrator's FMA contractions.
+struct PhysK {
+  float kc, dc, df, rest_t, bounce;  // contact_stiffness, contact_damping, friction_damping, terrain_restitution,
+                                     // bounce_threshold (CP)
+  float self_k;                      // self_stiffness
+};  // (the joint limits' constants are left to the compiler: it loads them far ahead of the backward pass)
+__device__ __forceinline__ PhysK sub_consts(CCfg* __restrict__ cfg) {
+  PhysK K = {cfg->contact_stiffness, cfg->contact_damping, cfg->friction_damping, cfg->terrain_restitution,
+             cfg->bounce_threshold, cfg->self_stiffness};
+  pin_s(K.kc); pin_s(K.dc); pin_s(K.df); pin_s(K.rest_t); pin_s(K.bounce); pin_s(K.self_k);
+  return K;
+}
+// What the control step's first sim step chooses and the later ones reuse, in registers of the lane (both were
+// round trips through the env's LDS scratch on every sim step): the deepest-point parameters of the lane's two
+// capsule segments (seg_deepest2; the lane's own values) and the trunk faces' two vertices (face_scan; face_key_max
+// leaves the same choice on all 16 lanes of the env).
+struct Held {
+  f2 ts;
+  int face[2];
+};
+
 // One integrator step of length h for the env of this lane.  Lane layout (16 per env): lane = 16 role + 4 env +
 // leg.  The four roles of a leg compute the leg's kinematics and ABA passes redundantly (base quantities on all 16
 // lanes), and split the leg's contact geometry two per lane (x, y halves of f2), each a capsule segment acting at
@@ -39,7 +71,9 @@ struct Phys {
 // half's link (thigh, hip, calf, foot).
 // cf_raw: this lane's reported contact forces (x half with the own primitive's self-contact force, y half, the
 // trunk's self-collision reaction of the lane's box contact and, on one lane, the trunk faces').
-__device__ __forceinline__ void phys_substep(CCfg* __restrict__ cfg, const float* lds, Phys& S, const float* tau,
+// K: sub_consts(cfg); H: the control step's held choices, written when face_scan_now and read otherwise.
+__device__ __forceinline__ void phys_substep(CCfg* __restrict__ cfg, const PhysK& K, Held& H, const float* lds,
+                                             Phys& S, const float* tau,
                                              float h, const float* g, float friction, float restitution,
                                              float payload, const Terr& T, int leg, int role, bool cf_out,
                                              float* cf_raw, float* self_sc, bool face_scan_now) {
@@ -57,8 +91,7 @@ __device__ __forceinline__ void phys_substep(CCfg* __restrict__ cfg, const float
     LC[i] = p == 0 ? GO1_LEG_FL[i] : GO1_LEG_FL[i] * (p == 1 ? msx : (p == 2 ? msy : msxy));
   }
   MARK(phys_begin);
-  const CP C = {cfg->contact_stiffness, cfg->contact_damping, cfg->friction_damping, friction,
-                0.5f * (restitution + cfg->terrain_restitution), cfg->bounce_threshold};
+  const CP C = {K.kc, K.dc, K.df, friction, 0.5f * (restitution + K.rest_t), K.bounce};
   float R[9];
   quat_to_R(S.quat, R);
   f2 vbp[3];  // base-frame (angular, linear) velocity pairs: R^T on both halves at once
@@ -68,17 +101,8 @@ __device__ __forceinline__ void phys_substep(CCfg* __restrict__ cfg, const float
   const float* th = model + 13 * 10 + 4 * 9 + 3 + 1;  // trunk half extents
 #ifndef GO1_ABL_NO_FACES
   // the trunk faces' vertices of the control step (face_scan), chosen here where few values are live yet (wave-uniform
-  // condition); one lane stores them for every sim step's face_force below (the same on the env's 16 lanes)
-  if (T.patch && face_scan_now) {
-    int sel[2];
-    face_scan(T, R, S.pos, th, 4 * role + leg, sel);
-    if (role == 0 && leg == 0) {
-      int* fsel = reinterpret_cast<int*>(self_sc + FACE_SEL_OFF);
-      fsel[0] = sel[0];
-      fsel[1] = sel[1];
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the env's other lanes read them (face_force)
-  }
+  // condition) and held for every sim step's face_force below
+  if (T.patch && face_scan_now) face_scan(T, R, S.pos, th, 4 * role + leg, H.face);
 #endif
   // ---- this leg: kinematics, rigid bias forces and gravity (hip -> calf)
   const float* origin = LC + 30;
@@ -202,7 +226,7 @@ __device__ __forceinline__ void phys_substep(CCfg* __restrict__ cfg, const float
     float wb[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, Mo[3] = {0.0f, 0.0f, 0.0f};
     MARK(self_begin);
 #ifndef GO1_ABL_NO_SELF  // ablation build only: no self-collision
-    const bool self_on = cfg->self_stiffness > 0.0f;
+    const bool self_on = K.self_k > 0.0f;
     int mask;
     {
       // the hip capsule's ends in the trunk frame: the hip joint + Rx(q) (0, y, 0)
@@ -281,8 +305,7 @@ __device__ __forceinline__ void phys_substep(CCfg* __restrict__ cfg, const float
         wB[i] = ps[i] + Rs[3 * i] * lpB[0] + Rs[3 * i + 1] * lpB[1] + Rs[3 * i + 2] * lpB[2];
       }
       MARK(seg_begin);
-      // the search once per control step (wave-uniform), its t held in the env's LDS scratch for the other sim steps
-      float2* held = reinterpret_cast<float2*>(self_sc + SEG_T_OFF) + (4 * role + leg);
+      // the search once per control step (wave-uniform), its t held (H.ts) for the other sim steps
       f2 ts;
       if (face_scan_now) {
 #ifdef GO1_ABL_NO_WALK  // ablation build only: every segment at its first end
@@ -292,10 +315,9 @@ __device__ __forceinline__ void phys_substep(CCfg* __restrict__ cfg, const float
 #else
         ts = seg_deepest2(T, wA, wB, rr, cell);
 #endif
-        *held = make_float2(ts.x, ts.y);
+        H.ts = ts;
       } else {
-        const float2 hv = *held;
-        ts = f2{hv.x, hv.y};
+        ts = H.ts;
       }
       MARK(seg_done);
 #pragma unroll
@@ -538,10 +560,8 @@ __device__ __forceinline__ void phys_substep(CCfg* __restrict__ cfg, const float
 #else
   if (T.patch) {  // the tunnel; on the plane the corners are the faces' deepest points
 #endif
-    // the vertices chosen at the control step's first sim step (at the top of phys_substep) from the env's LDS scratch
-    const int* fsel = reinterpret_cast<const int*>(self_sc + FACE_SEL_OFF);
-    const int sel[2] = {fsel[0], fsel[1]};
-    face_force(T, C, R, S.pos, vb, th, sel, wface, Fface);
+    // the vertices chosen at the control step's first sim step (at the top of phys_substep)
+    face_force(T, C, R, S.pos, vb, th, H.face, wface, Fface);
   }
   MARK(faces_done);
   // ---- base: rigid inertia + quad sum of the four legs and the trunk corners

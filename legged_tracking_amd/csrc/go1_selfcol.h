@@ -21,9 +21,9 @@
 // the trunk box and the leg's own folded links; a wave whose envs have no candidate is done.  Otherwise, per env in
 // LDS: the 16 primitives as (P0, r), (P1, 0), (V0, 0), (V1, 0) (segment ends and their velocities, world), and each
 // lane sums the forces on its own primitive from its candidate partners (self_narrow).
+// (+ 36 floats of padding: they held the control step's face vertices and capsule parameters, now registers
+// (go1_phys.h Held), and keep the four envs' records 4 banks apart as before)
 #define SELF_ENV_FLOATS (16 * 16 + 4 + 32)
-#define FACE_SEL_OFF (16 * 16)  // then the trunk faces' two vertices of the control step (face_scan)
-#define SEG_T_OFF (16 * 16 + 4)  // then the capsules' deepest-point parameters of the control step, (x, y) per lane
 
 // the lane's own primitive into this env's LDS scratch; rb: the radius of its bounding sphere about the segment's middle
 // (half the segment plus r), for the narrow phase's first test

@@ -363,10 +363,10 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
   // ---------------- decimation loop (:82-88)
   float cf_raw[CF_RAW] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, cf_leg[9], cf_base[3], cf_hip[3];
-  step_substeps<INJ>(c, A, J, P, s_mlp, s_phys, T, s_self[el], cf_raw, KL, friction, restitution, payload, e, lane,
-                     CI(action_scale), CI(hip_scale_reduction), leg, role);
+  step_substeps<INJ, SPEC>(c, A, J, P, s_mlp, s_phys, T, s_self[el], cf_raw, KL, friction, restitution, payload, e,
+                           lane, CI(action_scale), CI(hip_scale_reduction), leg, role, CI(decimation), CI(n_internal));
+  hold(false);  // (the reads first: they land under the contact totals' cross-lane sums)
   contact_totals<INJ>(cf_raw, A.inj_contact, e, leg, role, cf_leg, cf_base, cf_hip);
-  hold(false);
   float root[13];
   if (INJ) {
 #pragma unroll
@@ -1037,9 +1037,9 @@ static bool spec_match(const go1_config& c) {
 #define GO1_SPEC_CHECK(f, v) m = m && spec_eq(c.f, (decltype(c.f))(v));
   GO1_SPEC_FIELDS(GO1_SPEC_CHECK)
 #undef GO1_SPEC_CHECK
-  // the specialised kernel keeps GO1_LAG_STEPS(4) = 2 stored lag entries in registers (the sub-step
-  // loop itself stays run-time)
-  return m && c.decimation == 4;
+  // the specialised kernel keeps GO1_LAG_STEPS(4) = 2 stored lag entries in registers
+  static_assert(GO1_LAG_STEPS(GO1_SPEC_decimation) == 2, "go1_step_kernel<SPEC>: KMAX = KL = 2");
+  return m;
 }
 // the scan counts with kernels that keep the scan in registers (KPTS 7 / 15); any other grid is streamed
 static bool scan_compiled_in(const go1_config& c) { return c.scan_nx == GO1_GRID_X && c.scan_ny == GO1_GRID_Y; }

@@ -52,22 +52,39 @@ __device__ __forceinline__ void phys_store_root(const Phys& P, float* root) {
 // self-collision scratch; cf_raw: the last sub-step's per-lane contact forces (cf_sum).  action_scale and
 // hip_scale_reduction by value: the specialised trajectory kernel passes its compile-time constants.  leg and
 // role are the caller's own values: derived here again from lane they were a second live copy (+8 AGPRs).
-template <bool INJ, int KMAX, class Args>
+// dec, n_int: go1_config.decimation and n_internal by value.  FIXED: they are compile-time constants (the
+// specialised trajectory kernel; both loops stay rolled); otherwise they are read here once and pinned in SGPRs.
+// What a sim step's common path reads from the config right before using it (the step length, the contact and
+// self-collision constants: sub_consts) is read once, in front of the loop: through the constant address space the
+// compiler re-loads an invariant field at each use rather than keep it, a scalar-cache round trip with a wait per
+// sim step that a single wave per SIMD cannot hide.
+template <bool INJ, bool FIXED, int KMAX, class Args>
 __device__ __forceinline__ void step_substeps(CCfg* c, const Args& A, const Joints<KMAX>& J, Phys& P,
                                               const float* s_mlp, const float* s_phys, const Terr& T, float* s_self,
                                               float* cf_raw, int KL, float friction, float restitution,
                                               float payload, int e, int lane, float action_scale,
-                                              float hip_scale_reduction, int leg, int role) {
-  const int lq = lane >> 4, n = c->n_envs, dec = c->decimation;
+                                              float hip_scale_reduction, int leg, int role, int dec, int n_int) {
+  const int lq = lane >> 4, n = c->n_envs;
+  if (!FIXED) { pin_s(dec); pin_s(n_int); }
+  float h = c->sim_dt / (float)n_int;  // the integrator's step
+  pin_s(h);
+  const PhysK PK = sub_consts(c);
+  Held H = {f2{0.0f, 0.0f}, {-1, -1}};  // set by the control step's first sim step (phys_substep)
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     J.scaled[j] = J.act[j] * action_scale;
     if (j == 0) J.scaled[j] = J.scaled[j] * hip_scale_reduction;
   }
+#pragma unroll 1
   for (int sub = 0; sub < dec; ++sub) {
     MARK(sub_begin);
     // _compute_torques (:957-996)
     {
+#ifndef GO1_ABL_NO_MLP
+      // the parked fragments' reads first: they land under the input preparation below
+      MlpFrag Fs;
+      mlp_unpark(Fs, s_mlp, lane);
+#endif
       // inputs of this lane's three joints ...
       // the ring's oldest slot after this sub-step's push (:973-974) is old slot sub + 1, i.e. the
       // scaled action of `back` steps ago (stored entry KL - back), or this step's for back = 0
@@ -100,11 +117,7 @@ __device__ __forceinline__ void step_substeps(CCfg* c, const Args& A, const Join
 #pragma unroll
       for (int j = 0; j < 3; ++j) tq[j] = 0.0f * (b0[j] + b1v[j]);  // ablation build only: no actuator net
 #else
-      {
-        MlpFrag Fs;
-        mlp_unpark(Fs, s_mlp, lane);
-        mlp_group3(Fs, b0, b1v, tq);
-      }
+      mlp_group3(Fs, b0, b1v, tq);
 #endif
 #ifdef GO1_ABL_NO_MLP
 #pragma unroll
@@ -130,15 +143,15 @@ __device__ __forceinline__ void step_substeps(CCfg* c, const Args& A, const Join
         J.qd[j] = id[(leg * 3 + j) * 2 + 1];
       }
     } else {
-      const float h = c->sim_dt / (float)c->n_internal;
 #pragma unroll
       for (int j = 0; j < 3; ++j) { P.q[j] = J.q[j]; P.qd[j] = J.qd[j]; }
       MARK(phys_call);
 #ifndef GO1_ABL_NO_PHYS
-      for (int k = 0; k < c->n_internal; ++k) {
-        const bool last = (sub == dec - 1) && (k == c->n_internal - 1);
-        phys_substep(c, s_phys, P, J.torque, h, A.sim_gravity, friction, restitution, payload, T, leg, role, last,
-                     cf_raw, s_self, sub == 0 && k == 0);
+#pragma unroll 1
+      for (int k = 0; k < n_int; ++k) {
+        const bool last = (sub == dec - 1) && (k == n_int - 1);
+        phys_substep(c, PK, H, s_phys, P, J.torque, h, A.sim_gravity, friction, restitution, payload, T, leg, role,
+                     last, cf_raw, s_self, sub == 0 && k == 0);
       }
 #else
       P.qd[0] += 1e-4f * J.torque[0]; P.qd[1] += 1e-4f * J.torque[1]; P.qd[2] += 1e-4f * J.torque[2];

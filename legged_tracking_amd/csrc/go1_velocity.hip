@@ -260,8 +260,8 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
   // ---------------- decimation loop (:76-82): lag ring pushed per sim step (:940-942)
   float cf_raw[CF_RAW] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, cf_leg[9], cf_base[3], cf_hip[3];
-  step_substeps<INJ>(c, A, J, P, s_mlp, nullptr, T, s_self[el], cf_raw, VLAG, friction, restitution, payload, e, lane,
-                     c->action_scale, c->hip_scale_reduction, leg, role);
+  step_substeps<INJ, false>(c, A, J, P, s_mlp, nullptr, T, s_self[el], cf_raw, VLAG, friction, restitution, payload, e,
+                            lane, c->action_scale, c->hip_scale_reduction, leg, role, c->decimation, c->n_internal);
   // the commands are first read by the post-physics (the gait clock): loaded here, not with the prologue, so
   // that they do not occupy 15 registers through the sub-steps (the self-collision narrow phase needs them)
   float cmd[GO1_VEL_NUM_COMMANDS];
