@@ -14,6 +14,15 @@
  * for the default AC_Args architecture (actor_critic.py:21-93): adaptation module hist -> 256 -> 128 -> priv,
  * actor [hist, latent] -> 512 -> 256 -> 128 -> actions, critic [hist, priv] -> 512 -> 256 -> 128 -> 1, ELU.
  *
+ * The height-map encoder module (go1_gym_learn/ppo_cse_cnn, go1_ppo_dims.enc_mode = GO1_PPO_ENC_MLP; ABI 2): the
+ * heads read x = [s | s | emb] in place of the history, s the num_obs - n_map scalars of the LAST frame of a row and
+ *   emb = ELU(W1 ELU(W0 map + b0) + b1),  map -> 256 -> n_embed,
+ * the encoder of actor_critic.py:47-52 on that frame's n_map map values.  The encoder runs once per phase and takes
+ * the sum of the gradients that reach emb through the actor, the critic and the adaptation module (the reference
+ * runs it three times and sums three weight gradients; the earlier frames add exact zeros).  ppo_cse_cnn/ppo.py:44-46
+ * builds both optimizers over every parameter and the adaptation loss back-propagates through the encoder
+ * (:170-190), so the adaptation optimizer's slice is encoder + adaptation module.
+ *
  * Arithmetic: the GEMMs run on v_mfma_f32_16x16x32_f16 with every f32 operand split into hi + lo f16 halves
  * after an exact power-of-two scaling per tensor (3 MFMAs per product: hi*hi + hi*lo + lo*hi, f32
  * accumulation); everything else (biases, ELU, the loss, its gradient, reductions, Adam) is f32 / f64 VALU.
@@ -32,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GO1_PPO_ABI_VERSION 1
+#define GO1_PPO_ABI_VERSION 2
 #define GO1_PPO_OK 0
 #define GO1_PPO_E_ARG -1
 #define GO1_PPO_E_HIP -2
@@ -43,6 +52,12 @@ extern "C" {
 #define GO1_PPO_H1 512
 #define GO1_PPO_H2 256
 #define GO1_PPO_H3 128
+/* the encoder in front of the heads (go1_ppo_dims.enc_mode) */
+#define GO1_PPO_ENC_NONE 0
+#define GO1_PPO_ENC_MLP 1
+#define GO1_PPO_ENC_HIDDEN 256   /* the MLP encoder's hidden width */
+#define GO1_PPO_ENC_MAX_MAP 4096
+#define GO1_PPO_ENC_MAX_EMBED 512
 /* aux sums at the head of the gradient buffer: surrogate, value, KL (phase 0); adaptation, adaptation
    test (phase 1); all-reduced together with the gradients */
 #define GO1_PPO_AUX 8
@@ -53,6 +68,14 @@ typedef struct go1_ppo_dims {
   int32_t actions;  /* num_actions, 1..16 */
   int32_t mb;       /* mini-batch rows (num_envs * num_steps_per_env / num_mini_batches) */
   int64_t rows;     /* storage rows (num_steps_per_env * num_envs); every idx value < rows */
+  /* ABI 2, all zero: the plain module.  With enc_mode = GO1_PPO_ENC_MLP `hist` stays the stored history width, a
+     multiple of num_obs, and the heads' input width is 2 (num_obs - n_map) + n_embed.  Refused (GO1_PPO_E_ARG): any
+     other enc_mode, n_embed not a multiple of 128 or above 512, n_map outside 1..min(4096, num_obs), hist not a
+     multiple of num_obs. */
+  int32_t enc_mode;
+  int32_t num_obs;  /* width of one observation frame: [scalars | map] */
+  int32_t n_map;    /* prod(height_map_shape), the trailing columns of a frame */
+  int32_t n_embed;  /* cnn_num_embedding */
 } go1_ppo_dims;
 
 /* PPO_Args / Adam hyper-parameters, as floats in device memory (the caller rewrites them when they change) */
@@ -74,11 +97,13 @@ typedef struct go1_ppo_bufs {
   const float *privileged_obs, *actions, *values, *advantages, *returns, *actions_log_prob, *mu, *sigma;
   const int64_t* idx;            /* (mb) storage rows of the mini-batch (mini_batch_generator's permutation slice) */
   /* flat f32 parameters in state_dict order (adaptation_module.{0,2,4}, actor_body.{0,2,4,6},
-     critic_body.{0,2,4,6}, each weight then bias; std last): go1_ppo_param_count() floats */
+     critic_body.{0,2,4,6}, each weight then bias; std last): go1_ppo_param_count() floats.  With an encoder its
+     parameters lead: height_map_encoder.model.{0,2}, then the above (the module's own order has std first) */
   float* params;
   float* grads;                  /* GO1_PPO_AUX + go1_ppo_param_count() floats: aux sums, then the flat gradient */
   float *exp_avg, *exp_avg_sq;   /* PPO.optimizer Adam state, flat like params */
-  float *ad_exp_avg, *ad_exp_avg_sq; /* adaptation_module_optimizer Adam state, flat over the adaptation module */
+  float *ad_exp_avg, *ad_exp_avg_sq; /* adaptation_module_optimizer Adam state, flat over the leading slice
+                                        (adaptation module; encoder + adaptation module with an encoder) */
   float* steps;                  /* [2] Adam step counts (torch's state['step']): main, adaptation */
   double* lr;                    /* [1] the adaptive learning rate of PPO.optimizer (f64, as the reference's floats) */
   const go1_ppo_hyper* hyper;    /* device memory */
@@ -92,7 +117,8 @@ int go1_ppo_abi_version(void);
  * mirrors (go1_ppo_hyper is one float per field). */
 void go1_ppo_abi_sizes(int64_t out[3]);
 const char* go1_ppo_last_error(void);
-/* number of parameters (floats), and of the adaptation module's (the leading slice) */
+/* number of parameters (floats), and of the adaptation optimizer's leading slice (the adaptation module's; with an
+   encoder, the encoder's and the adaptation module's) */
 int go1_ppo_param_count(const go1_ppo_dims* d, int64_t* total, int64_t* adaptation);
 int go1_ppo_workspace_bytes(const go1_ppo_dims* d, int64_t* bytes);
 /* split + pack the GEMM weights from params (after any change of params outside go1_ppo_step) */

@@ -20,6 +20,18 @@
 //   reduce  partials -> flat gradient (+ loss / KL sums); [all-reduce at world > 1]
 //   norm, finalize (KL -> learning rate, clip_grad_norm_), adam (all parameters), pack
 //
+// With the height-map encoder in front of the heads (go1_ppo_dims.enc_mode = GO1_PPO_ENC_MLP; ppo_cse_cnn) the
+// gathered row is G = [emb (E) | s | s | latent | priv]: s the scalars of the row's last frame, emb the encoder's
+// output, first so that the xw kernel writes it in place with 16-byte stores (the module's column order is
+// [s | s | emb]: pack_kernel maps the first layers' weight columns, reduce's segments map their gradients back).
+//   phase 0  gather<ENC> (scalars, the map into its own padded buffer); xw<F> map -> e1 (256), xw<F> e1 -> emb into
+//            G; the heads as above; then xw<LIN> W_P0[:, emb]^T delta1p, W_C0[:, emb]^T delta1c, W_A0[:, emb]^T
+//            delta1a, embgrad (their sum * ELU'(emb), column sums), xw<D> delta e1; the two encoder weight
+//            gradients join the grouped wgrad launch.  One encoder pass serves the three heads.
+//   phase 1  xw<F> x 2 again (the encoder's weights moved in step 0), the adaptation module as above, xw<D> d emb =
+//            (W_A0[:, emb]^T delta1a) * ELU'(emb), xw<D> delta e1, wgrad of four layers; Adam and the re-pack
+//            cover encoder + adaptation module (the adaptation optimizer's slice, with its own moments).
+//
 // GEMMs ("xw": activations x weights^T, "wgrad": delta^T x activations) run on v_mfma_f32_16x16x32_f16 with
 // f32 accuracy from the 3xF16 split (hi = f16(x), lo = f16(x - hi), products hi*hi + hi*lo + lo*hi, f32
 // accumulation; the dropped lo*lo term is ~2^-22 of a product).  Every operand tensor is first scaled by an
@@ -378,8 +390,9 @@ struct WgProb {
   int32_t kpad;       // row length of the partial (multiple of TB)
   int32_t tiles_k, tiles_n, tile0;
 };
+constexpr int MAX_WG = 10;  // phase 0 with an encoder: six head layers, two adaptation layers, two encoder layers
 struct WgLaunch {
-  WgProb p[8];
+  WgProb p[MAX_WG];
   int32_t nprob, M, S, chunk, total;
 };
 
@@ -416,7 +429,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgLaunch L) {
   }
   int pi = 0;
 #pragma unroll
-  for (int i = 1; i < 8; ++i)
+  for (int i = 1; i < MAX_WG; ++i)
     if (i < L.nprob && t >= L.p[i].tile0) pi = i;
   const WgProb& P = L.p[pi];
   const int lt = t - P.tile0, tk = lt / P.tiles_n, tn = lt - tk * P.tiles_n;
@@ -546,26 +559,36 @@ struct GatherArgs {
   float* G;
   float* B;
   uint32_t* mx;
+  // ENC: the heads' input columns of G are [embedding E (written by the encoder) | scalars S | scalars S], H = E + 2 S,
+  // the scalars those of the last frame (columns foff .. foff + S of a history row); its map (the NM columns after
+  // the scalars) goes to Mp rows of ldm floats, zero-padded
+  int32_t E, S, foff, NM, ldm;
+  float* Mp;
+  uint32_t* mxmap;
 };
 
 // A wave gathers four rows at a time (rows strided over the grid): the four storage indices come in one load,
 // then every element load of the four rows is issued (clamped addresses, selects afterwards) before any store.
 // One atomicMax per workgroup: a max per row-block would serialise ~M atomics on one address.
 constexpr int GATHER_BLOCKS_MAX = 1024;
+template <bool ENC>
 __global__ __launch_bounds__(256) void gather_kernel(GatherArgs g) {
   __shared__ uint32_t red[4];
+  __shared__ uint32_t redm[4];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int M = g.M, H = g.H, P = g.P, A = g.A, ldg = g.ldg, bw = g.bw;
   const int nwaves = gridDim.x * 4;
-  uint32_t mb = 0u;
+  uint32_t mb = 0u, mm = 0u;
   for (int m0 = (blockIdx.x * 4 + w) * 4; m0 < M; m0 += nwaves * 4) {
     const int64_t ri = g.idx[min(m0 + (lane & 3), M - 1)];
     int64_t r[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) r[j] = __shfl(ri, j);
-    for (int k0 = 0; k0 < ldg; k0 += 64) {
+    for (int k0 = ENC ? g.E : 0; k0 < ldg; k0 += 64) {  // E is a multiple of 128
       const int k = k0 + lane;
-      const int kh = min(k, H - 1), kp = min(max(k - H - P, 0), P - 1);
+      const int ks = k - g.E - (k - g.E >= g.S ? g.S : 0);  // ENC: the scalar of column k (both copies)
+      const int kh = ENC ? g.foff + min(max(ks, 0), max(g.S - 1, 0)) : min(k, H - 1);
+      const int kp = min(max(k - H - P, 0), P - 1);
       const bool in_h = k < H, in_p = k >= H + P && k < H + 2 * P;
       float vh[4], vp[4];
 #pragma unroll
@@ -579,6 +602,23 @@ __global__ __launch_bounds__(256) void gather_kernel(GatherArgs g) {
         if (m0 + j < M && k < ldg) {
           g.G[(size_t)(m0 + j) * ldg + k] = v;
           mb = max(mb, absbits(v));
+        }
+      }
+    }
+    if (ENC) {
+      for (int k0 = 0; k0 < g.ldm; k0 += 64) {
+        const int k = k0 + lane;
+        const int km = g.foff + g.S + min(k, g.NM - 1);
+        float vm[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) vm[j] = g.hist[r[j] * g.hld + km];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float v = k < g.NM ? vm[j] : 0.0f;
+          if (m0 + j < M && k < g.ldm) {
+            g.Mp[(size_t)(m0 + j) * g.ldm + k] = v;
+            mm = max(mm, absbits(v));
+          }
         }
       }
     }
@@ -604,12 +644,73 @@ __global__ __launch_bounds__(256) void gather_kernel(GatherArgs g) {
     }
   }
   mb = wave_max_u32(mb);
-  if (lane == 0) red[w] = mb;
+  if (ENC) mm = wave_max_u32(mm);
+  if (lane == 0) {
+    red[w] = mb;
+    if (ENC) redm[w] = mm;
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
     mb = max(max(red[0], red[1]), max(red[2], red[3]));
     if (mb) atomicMax(g.mx, mb);
+    if (ENC) {
+      mm = max(max(redm[0], redm[1]), max(redm[2], redm[3]));
+      if (mm) atomicMax(g.mxmap, mm);
+    }
   }
+}
+
+// ------------------------------------------------------------------ the embedding's gradient (phase 0)
+// d emb = (t_p + t_c + t_a) * ELU'(emb): the three products W[:, emb]^T delta1 of the actor, the critic and the
+// adaptation module (xw<LIN> outputs, summed in that order), with the column sums (the encoder's output bias
+// gradient) per 128-row tile in a fixed order and max |d emb|.  Grid (row tiles, E / 128); a thread owns four
+// columns of the rows rl, rl + 8, ... of its tile.
+struct EmbArgs {
+  const float *tp, *tc, *ta;  // [M][E]
+  const float* emb;           // the forward embedding (G's leading columns), row stride lde
+  int64_t lde;
+  float* demb;                // [M][E]
+  float* colsum;              // [tiles_m][E]
+  uint32_t* dmax;
+  int32_t M, E;
+};
+
+__global__ __launch_bounds__(256) void embgrad_kernel(EmbArgs a) {
+  __shared__ f4_t red[8][32];
+  __shared__ uint32_t smax[4];
+  const int tid = threadIdx.x, c4 = tid & 31, rl = tid >> 5;
+  const int mt = blockIdx.x, n = blockIdx.y * TB + 4 * c4;
+  f4_t cs = (f4_t){0.0f, 0.0f, 0.0f, 0.0f};
+  uint32_t mx = 0u;
+#pragma unroll 4
+  for (int i = 0; i < TB / 8; ++i) {
+    const int m = mt * TB + rl + 8 * i;
+    const bool in = m < a.M;
+    const size_t o = (size_t)min(m, a.M - 1) * a.E + n;
+    const f4_t tp = *reinterpret_cast<const f4_t*>(a.tp + o);
+    const f4_t tc = *reinterpret_cast<const f4_t*>(a.tc + o);
+    const f4_t ta = *reinterpret_cast<const f4_t*>(a.ta + o);
+    const f4_t e = *reinterpret_cast<const f4_t*>(a.emb + (size_t)min(m, a.M - 1) * a.lde + n);
+    f4_t v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[j] = in ? ((tp[j] + tc[j]) + ta[j]) * delu_from_out(e[j]) : 0.0f;
+      mx = max(mx, absbits(v[j]));
+    }
+    cs += v;
+    if (in) *reinterpret_cast<f4_t*>(a.demb + o) = v;
+  }
+  red[rl][c4] = cs;
+  mx = wave_max_u32(mx);
+  if ((tid & 63) == 0) smax[tid >> 6] = mx;
+  __syncthreads();
+  if (rl == 0) {
+    f4_t s = red[0][c4];
+#pragma unroll
+    for (int j = 1; j < 8; ++j) s += red[j][c4];
+    *reinterpret_cast<f4_t*>(a.colsum + (size_t)mt * a.E + n) = s;
+  }
+  if (tid == 0) atomicMax(a.dmax, max(max(smax[0], smax[1]), max(smax[2], smax[3])));
 }
 
 __device__ __forceinline__ float half_sum(float v) {  // sum over the 32 lanes of a half-wave
@@ -1049,7 +1150,7 @@ struct Seg {
   int64_t lds, pstride, ldd;          // source row stride, partial stride, destination row stride
   int32_t rows, cols, nparts, start;  // start: first flat element of the segment in the launch
 };
-constexpr int MAX_SEGS = 32;
+constexpr int MAX_SEGS = 40;  // phase 0 with an encoder: 33
 struct SegTable {
   Seg s[MAX_SEGS];
   int32_t nseg, total;
@@ -1115,8 +1216,8 @@ struct Finalize {
   float* steps;
   double* losses;
   float* scal;
-  uint32_t* zero[3];  // max slots to clear for the launches that follow: zero[i][0 .. nz[i])
-  int32_t nz[3];
+  uint32_t* zero[6];  // max slots to clear for the launches that follow: zero[i][0 .. nz[i])
+  int32_t nz[6];
 };
 
 __global__ __launch_bounds__(256) void finalize_kernel(Finalize F) {
@@ -1124,7 +1225,7 @@ __global__ __launch_bounds__(256) void finalize_kernel(Finalize F) {
   const go1_ppo_hyper hp = *F.hyper;
   const double world = hp.world > 0.0f ? (double)hp.world : 1.0;
 #pragma unroll
-  for (int i = 0; i < 3; ++i)
+  for (int i = 0; i < 6; ++i)
     if ((int)threadIdx.x < F.nz[i]) F.zero[i][threadIdx.x] = 0u;
   double s = 0.0;
   if (F.phase == 0) s = F.norm_part[threadIdx.x];
@@ -1204,14 +1305,17 @@ struct PackW {
   const float* w;  // source (n, k - gap) with row stride ldw; image column kk reads source column kk (kk < gap_at),
                    // nothing (gap_at <= kk < gap_at + gap: zero weights), kk - gap (beyond)
   int32_t n, k, ldw, gap_at, gap, G, npad;
+  // the encoder module's first layers: the image's (and G's) leading perm_p columns are [embedding perm_e | scalars],
+  // the source's [scalars | embedding]; perm_p = 0: none
+  int32_t perm_e, perm_p;
   h8_t* img;       // forward image [G][2][4][npad][8]
-  h8_t* imgt;      // transposed image [ceil(n / 32)][2][4][kpadT][8] or NULL
+  h8_t* imgt;      // transposed image [ceil(n / 32)][2][4][npadt][8] of the image's first npadt columns, or NULL
   int32_t Gt, npadt;
   uint32_t* wmax;
   int32_t* wexp;
   int32_t start;   // first element of this tensor in the launch
 };
-constexpr int MAX_PACK = 8;
+constexpr int MAX_PACK = 10;
 struct PackTable {
   PackW t[MAX_PACK];
   int32_t nt, total;
@@ -1247,7 +1351,9 @@ __global__ __launch_bounds__(256) void pack_kernel(PackTable T) {
   const int es = scale_exp(*W.wmax);
   if (le == 0) *W.wexp = es;
   const bool in_gap = k >= W.gap_at && k < W.gap_at + W.gap;
-  const float x = in_gap ? 0.0f : ldexpf(W.w[(size_t)n * W.ldw + (k < W.gap_at ? k : k - W.gap)], es);
+  int ks = k < W.gap_at ? k : k - W.gap;
+  if (ks < W.perm_p) ks = ks < W.perm_e ? ks + (W.perm_p - W.perm_e) : ks - W.perm_e;
+  const float x = in_gap ? 0.0f : ldexpf(W.w[(size_t)n * W.ldw + ks], es);
   const _Float16 hi = (_Float16)__builtin_amdgcn_cvt_pkrtz(x, 0.0f)[0];
   const _Float16 lo = (_Float16)__builtin_amdgcn_cvt_pkrtz(x - (float)hi, 0.0f)[0];
   {
@@ -1256,7 +1362,7 @@ __global__ __launch_bounds__(256) void pack_kernel(PackTable T) {
     base[(((size_t)(g * 2 + 0) * 4 + q) * W.npad + n) * 8 + r] = hi;
     base[(((size_t)(g * 2 + 1) * 4 + q) * W.npad + n) * 8 + r] = lo;
   }
-  if (W.imgt) {
+  if (W.imgt && k < W.npadt) {
     const int g = n >> 5, q = (n >> 3) & 3, r = n & 7;
     _Float16* base = reinterpret_cast<_Float16*>(W.imgt);
     base[(((size_t)(g * 2 + 0) * 4 + q) * W.npadt + k) * 8 + r] = hi;
@@ -1285,24 +1391,39 @@ enum MaxSlot {
   MX_G = 0,  // the gathered mini-batch rows (obs_history, privileged_obs)
   MX_LAT, MX_A1A, MX_A2A, MX_P1, MX_P2, MX_P3, MX_C1, MX_C2, MX_C3,
   MX_D3P, MX_D3C, MX_D2P, MX_D2C, MX_D1P, MX_D1C, MX_D2A, MX_D1A,
+  // the encoder: the gathered map, its hidden layer, d emb, d hidden.  The embedding's maximum goes to MX_LAT, the
+  // slot of G's computed columns (embedding, latent): the first layers' scale max(MX_G, MX_LAT) bounds it
+  MX_MAP, MX_E1, MX_DEMB, MX_DE1,
   MX_N
 };
-enum WSlot { W_A0 = 0, W_A2, W_P0, W_P2, W_P4, W_C0, W_C2, W_C4, W_N };
+enum WSlot { W_A0 = 0, W_A2, W_P0, W_P2, W_P4, W_C0, W_C2, W_C4, W_E0, W_E2, W_N };
+constexpr int W_PLAIN = W_E0;  // the slots of the plain module
+constexpr int ENC_H = GO1_PPO_ENC_HIDDEN;
 
 struct Lay {
-  int H, P, A, M, MP, MT, HB, ldg, bw;
+  int H, P, A, M, MP, MT, HB, ldg, bw;  // H: the heads' input width (hist; 2 SC + E with an encoder)
+  // the encoder (enc = 0: none): embedding width, scalars and map values of a frame, the map buffer's row stride,
+  // the stored history width and the last frame's first column in it; nW: weight slots in use
+  int enc, E, SC, NM, ldm, Hs, foff, nW;
   int S[2], chunk[2];  // weight-gradient row split per phase (about two workgroups per CU in one round)
   int64_t np_total, np_adapt;
   // parameter offsets (floats) in state_dict order
-  int64_t pw[11], pb[11], pstd;
+  int64_t pw[13], pb[13], pstd;  // indexed by IA0 .. IC6, IE0, IE2
   // workspace byte offsets
   size_t maxes, wmax, wexp, scal, normp, G, Bb, a1a, a2a, p1, p2, p3, c1, c2, c3, d3p, d3c, d2p, d2c, d1p, d1c, d2a,
       d1a, cs1a, cs1p, cs1c, cs2p, cs2c, hpart, apart, wpart[W_N], img[W_N], imgt[W_N], total;
+  size_t mapb, e1, demb, de1, tp, tc, ta, cse1, csemb, zbias;  // the encoder's buffers
   int64_t wpart_stride[W_N];
   int wn[W_N], wk[W_N];  // rows / GEMM columns of each weight image
+  int wkt[W_N];          // columns of the transposed image (0: none)
 };
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// parameter indices: a0 a2 a4 | p0 p2 p4 p6 | c0 c2 c4 c6 | the encoder's e0 e2 (first in the flat buffers)
+enum { IA0 = 0, IA2, IA4, IP0, IP2, IP4, IP6, IC0, IC2, IC4, IC6, IE0, IE2 };
+// one weight image per W slot: slot -> parameter index
+constexpr int kWParam[W_N] = {IA0, IA2, IP0, IP2, IP4, IC0, IC2, IC4, IE0, IE2};
 
 bool make_layout(const go1_ppo_dims* d, Lay& L, std::string& err) {
   if (!d || d->hist < 1 || d->priv < 1 || d->priv > 8 || d->actions < 1 || d->actions > 16 || d->mb < 1 ||
@@ -1310,7 +1431,37 @@ bool make_layout(const go1_ppo_dims* d, Lay& L, std::string& err) {
     err = "go1_ppo: dims outside the supported architecture (hist >= 1, priv 1..8, actions 1..16, mb <= rows)";
     return false;
   }
-  L.H = d->hist;
+  L.enc = d->enc_mode;
+  L.E = L.SC = L.NM = L.ldm = L.foff = 0;
+  L.Hs = L.H = d->hist;
+  L.nW = W_PLAIN;
+  if (d->enc_mode != GO1_PPO_ENC_NONE) {
+    if (d->enc_mode != GO1_PPO_ENC_MLP) {
+      err = "go1_ppo: enc_mode " + std::to_string(d->enc_mode) + " is not implemented (0: no encoder, 1: the MLP "
+            "encoder; the CNN encoder's backward is not on the engine)";
+      return false;
+    }
+    if (d->n_embed < TB || d->n_embed % TB != 0 || d->n_embed > GO1_PPO_ENC_MAX_EMBED) {
+      err = "go1_ppo: n_embed " + std::to_string(d->n_embed) + " is not implemented (a multiple of 128, at most 512)";
+      return false;
+    }
+    if (d->n_map < 1 || d->n_map > GO1_PPO_ENC_MAX_MAP || d->n_map > d->num_obs) {
+      err = "go1_ppo: n_map " + std::to_string(d->n_map) + " is not implemented (1..4096 map values, at most num_obs)";
+      return false;
+    }
+    if (d->hist % d->num_obs != 0) {
+      err = "go1_ppo: hist " + std::to_string(d->hist) + " is not a multiple of num_obs " + std::to_string(d->num_obs) +
+            " (whole frames; the encoder reads the last one)";
+      return false;
+    }
+    L.E = d->n_embed;
+    L.NM = d->n_map;
+    L.SC = d->num_obs - d->n_map;
+    L.H = 2 * L.SC + L.E;
+    L.foff = d->hist - d->num_obs;
+    L.ldm = cdiv(L.NM, 4) * 4;
+    L.nW = W_N;
+  }
   L.P = d->priv;
   L.A = d->actions;
   L.M = d->mb;
@@ -1325,6 +1476,18 @@ bool make_layout(const go1_ppo_dims* d, Lay& L, std::string& err) {
                            H1 * (H + P), H2 * H1, H3 * H2, 1 * H3};
   const int64_t bsz[11] = {HA1, HA2, P, H1, H2, H3, A, H1, H2, H3, 1};
   int64_t o = 0;
+  if (L.enc) {  // the encoder leads the flat buffers: the adaptation optimizer's slice is encoder + adaptation module
+    L.pw[IE0] = o;
+    o += (int64_t)ENC_H * L.NM;
+    L.pb[IE0] = o;
+    o += ENC_H;
+    L.pw[IE2] = o;
+    o += (int64_t)L.E * ENC_H;
+    L.pb[IE2] = o;
+    o += L.E;
+  } else {
+    L.pw[IE0] = L.pb[IE0] = L.pw[IE2] = L.pb[IE2] = 0;
+  }
   for (int i = 0; i < 11; ++i) {
     L.pw[i] = o;
     o += wsz[i];
@@ -1374,16 +1537,16 @@ bool make_layout(const go1_ppo_dims* d, Lay& L, std::string& err) {
   L.hpart = take((size_t)HEAD_BLOCKS * head_stride(L.A) * F);
   L.apart = take((size_t)ADAPT_BLOCKS * adapt_stride(L.P) * F);
   // weight-gradient partials [S][n][kpad] and weight images (4 bytes per element: hi + lo halves)
-  const int wn[W_N] = {HA1, HA2, H1, H2, H3, H1, H2, H3};
+  const int wn[W_N] = {HA1, HA2, H1, H2, H3, H1, H2, H3, ENC_H, L.E};
   // the row split of each phase's grouped weight-gradient launch: at most 512 workgroups (two per CU with the
   // launch's 64 KiB of LDS: one more would start a second round), chunks of >= 64 rows
   {
-    const int wk0[W_N] = {L.H, HA1, L.H + L.P, H1, H2, L.H + 2 * L.P, H1, H2};
+    const int wk0[W_N] = {L.H, HA1, L.H + L.P, H1, H2, L.H + 2 * L.P, H1, H2, L.NM, ENC_H};
     int tiles[2] = {0, 0};
-    for (int i = 0; i < W_N; ++i) {
+    for (int i = 0; i < L.nW; ++i) {
       const int t = cdiv(wk0[i], TB) * (wn[i] / TB);
       tiles[0] += t;
-      if (i == W_A0 || i == W_A2) tiles[1] += t;
+      if (i == W_A0 || i == W_A2 || i == W_E0 || i == W_E2) tiles[1] += t;
     }
     for (int ph = 0; ph < 2; ++ph) {
       int S = 512 / tiles[ph];
@@ -1394,27 +1557,39 @@ bool make_layout(const go1_ppo_dims* d, Lay& L, std::string& err) {
   }
   // GEMM columns: the actor's first layer reads [hist, latent], the critic's [hist, latent, priv] (zero weights on
   // the latent columns), the adaptation module's [hist]
-  const int wk[W_N] = {L.H, HA1, L.H + L.P, H1, H2, L.H + 2 * L.P, H1, H2};
-  for (int i = 0; i < W_N; ++i) {
+  const int wk[W_N] = {L.H, HA1, L.H + L.P, H1, H2, L.H + 2 * L.P, H1, H2, L.NM, ENC_H};
+  for (int i = 0; i < W_N; ++i) L.wn[i] = L.wk[i] = L.wkt[i] = 0;
+  for (int i = 0; i < L.nW; ++i) {
     L.wn[i] = wn[i];
     L.wk[i] = wk[i];
     const int kpad = cdiv(wk[i], TB) * TB;
     L.wpart_stride[i] = (int64_t)wn[i] * kpad;
-    const int S = (i == W_A0 || i == W_A2) ? std::max(L.S[0], L.S[1]) : L.S[0];
+    const int S = (i == W_A0 || i == W_A2 || i == W_E0 || i == W_E2) ? std::max(L.S[0], L.S[1]) : L.S[0];
     L.wpart[i] = take((size_t)S * wn[i] * kpad * F);
     L.img[i] = take((size_t)cdiv(wk[i], 32) * 32 * wn[i] * 4);
-    // transposed images for the layers the backward crosses: a2 (adaptation L2), p2, p4, c2, c4
-    const bool tr = i == W_A2 || i == W_P2 || i == W_P4 || i == W_C2 || i == W_C4;
-    L.imgt[i] = tr ? take((size_t)cdiv(wn[i], 32) * 32 * wk[i] * 4) : 0;
+    // transposed images for the layers the backward crosses: a2 (adaptation L2), p2, p4, c2, c4, the encoder's
+    // output layer; with an encoder, the embedding columns (the image's first E) of the three first layers
+    const bool tr = i == W_A2 || i == W_P2 || i == W_P4 || i == W_C2 || i == W_C4 || i == W_E2;
+    const bool tre = L.enc && (i == W_A0 || i == W_P0 || i == W_C0);
+    L.wkt[i] = tr ? wk[i] : (tre ? L.E : 0);
+    L.imgt[i] = L.wkt[i] ? take((size_t)cdiv(wn[i], 32) * 32 * L.wkt[i] * 4) : 0;
+  }
+  if (L.enc) {
+    const size_t E = (size_t)L.E;
+    L.mapb = take(MPs * L.ldm * F);
+    L.e1 = take(MPs * ENC_H * F);
+    L.demb = take(MPs * E * F);
+    L.de1 = take(MPs * ENC_H * F);
+    L.tp = take(MPs * E * F);
+    L.tc = take(MPs * E * F);
+    L.ta = take(MPs * E * F);
+    L.cse1 = take((size_t)L.MT * ENC_H * F);
+    L.csemb = take((size_t)L.MT * E * F);
+    L.zbias = take(GO1_PPO_ENC_MAX_EMBED * F);  // zeros (never written): the bias of the xw<LIN> products
   }
   L.total = b;
   return true;
 }
-
-// parameter indices: a0 a2 a4 | p0 p2 p4 p6 | c0 c2 c4 c6
-enum { IA0 = 0, IA2, IA4, IP0, IP2, IP4, IP6, IC0, IC2, IC4, IC6 };
-// one weight image per W slot: slot -> parameter index
-constexpr int kWParam[W_N] = {IA0, IA2, IP0, IP2, IP4, IC0, IC2, IC4};
 
 struct Ctx {
   const go1_ppo_dims* d;
@@ -1553,9 +1728,12 @@ void seg_w(const Ctx& C, SegBuilder& B, int wslot, int pi, int ldd, int phase) {
 int pack_weights(const Ctx& C, bool adaptation_only, bool zero_max) {
   const Lay& L = C.L;
   PackTable T{};
-  const int nw = adaptation_only ? 2 : W_N;
+  // adaptation_only: the adaptation optimizer's slice (with an encoder, the encoder's two layers as well)
+  const int ad_slots[4] = {W_A0, W_A2, W_E0, W_E2};
+  const int nw = adaptation_only ? (L.enc ? 4 : 2) : L.nW;
   uint32_t* wmax = C.at<uint32_t>(L.wmax);
-  for (int i = 0; i < nw; ++i) {
+  for (int j = 0; j < nw; ++j) {
+    const int i = adaptation_only ? ad_slots[j] : j;
     PackW& p = T.t[T.nt++];
     const int pi = kWParam[i];
     p.w = C.W(pi);
@@ -1564,12 +1742,15 @@ int pack_weights(const Ctx& C, bool adaptation_only, bool zero_max) {
     p.ldw = (pi == IC0) ? L.H + L.P : L.wk[i];
     p.gap_at = (pi == IC0) ? L.H : 0;  // the critic's image: zero weights on G's latent columns
     p.gap = (pi == IC0) ? L.P : 0;
+    const bool first = pi == IA0 || pi == IP0 || pi == IC0;
+    p.perm_e = (L.enc && first) ? L.E : 0;
+    p.perm_p = (L.enc && first) ? L.H : 0;
     p.G = cdiv(L.wk[i], 32);
     p.npad = L.wn[i];
     p.img = C.at<h8_t>(L.img[i]);
     p.imgt = L.imgt[i] ? C.at<h8_t>(L.imgt[i]) : nullptr;
     p.Gt = cdiv(L.wn[i], 32);
-    p.npadt = L.wk[i];
+    p.npadt = L.wkt[i];
     p.wmax = wmax + i;
     p.wexp = C.at<int32_t>(L.wexp) + i;
     p.start = T.total;
@@ -1629,7 +1810,7 @@ int adapt_forward(const Ctx& C) {
   float *G = C.at<float>(L.G), *a1a = C.at<float>(L.a1a), *a2a = C.at<float>(L.a2a);
   if ((rc = launch_xw(C, EPI_ELU,
                       xw_prob(C, G, L.ldg, L.H, C.mx(MX_G), W_A0, false, HA1, C.B(IA0), nullptr, 0, a1a, HA1,
-                              C.mx(MX_A1A), nullptr),
+                              C.mx(MX_A1A), nullptr, L.enc ? C.mx(MX_LAT) : nullptr),
                       nullptr)))
     return rc;
   return launch_xw(C, EPI_ELU,
@@ -1647,11 +1828,75 @@ int adapt_backward_l2(const Ctx& C) {
                    nullptr);
 }
 
+// the weight gradient of a first layer (W_A0, W_P0, W_C0): the partial's columns are the image's, G's
+void seg_first(const Ctx& C, SegBuilder& B, int wslot, int pi, int phase) {
+  const Lay& L = C.L;
+  const int n = L.wn[wslot], kpad = cdiv(L.wk[wslot], TB) * TB, H = L.H, P = L.P;
+  const int ldd = pi == IA0 ? H : H + P;
+  const float* wp = C.at<float>(L.wpart[wslot]);
+  auto add = [&](int dst_col, int src_col, int cols) {
+    if (cols > 0) B.add(C.gW(pi) + dst_col, wp + src_col, n, cols, kpad, L.S[phase], L.wpart_stride[wslot], ldd);
+  };
+  if (L.enc) {  // image [embedding | scalars | scalars] -> parameter [scalars | scalars | embedding]
+    add(0, L.E, 2 * L.SC);
+    add(2 * L.SC, 0, L.E);
+    if (pi == IP0) add(H, H, P);
+  } else {
+    add(0, 0, pi == IP0 ? H + P : H);
+  }
+  // the critic: G's priv columns (the latent columns' gradient is dropped)
+  if (pi == IC0) add(H, H + P, P);
+}
+
+// ------------------------------------------------------------------ the encoder (enc_mode = GO1_PPO_ENC_MLP)
+// forward: e1 = ELU(W0 map + b0), emb = ELU(W1 e1 + b1) into G's leading E columns (its maximum into MX_LAT)
+int encoder_forward(const Ctx& C) {
+  const Lay& L = C.L;
+  int rc;
+  float *e1 = C.at<float>(L.e1), *G = C.at<float>(L.G);
+  if ((rc = launch_xw(C, EPI_ELU,
+                      xw_prob(C, C.at<float>(L.mapb), L.ldm, L.NM, C.mx(MX_MAP), W_E0, false, ENC_H, C.B(IE0), nullptr,
+                              0, e1, ENC_H, C.mx(MX_E1), nullptr),
+                      nullptr)))
+    return rc;
+  return launch_xw(C, EPI_ELU,
+                   xw_prob(C, e1, ENC_H, ENC_H, C.mx(MX_E1), W_E2, false, L.E, C.B(IE2), nullptr, 0, G, L.ldg,
+                           C.mx(MX_LAT), nullptr),
+                   nullptr);
+}
+
+// delta e1 = (W1^T d emb) * ELU'(e1)
+int encoder_backward(const Ctx& C) {
+  const Lay& L = C.L;
+  return launch_xw(C, EPI_DELU,
+                   xw_prob(C, C.at<float>(L.demb), L.E, L.E, C.mx(MX_DEMB), W_E2, true, ENC_H, nullptr,
+                           C.at<float>(L.e1), ENC_H, C.at<float>(L.de1), ENC_H, C.mx(MX_DE1), C.at<float>(L.cse1)),
+                   nullptr);
+}
+
+// the encoder's two weight-gradient problems, appended to a grouped launch
+int encoder_wg(const Ctx& C, WgProb* ps) {
+  const Lay& L = C.L;
+  ps[0] = wg_prob(C, W_E2, C.at<float>(L.e1), ENC_H, ENC_H, C.mx(MX_E1), C.at<float>(L.demb), L.E, L.E,
+                  C.mx(MX_DEMB));
+  ps[1] = wg_prob(C, W_E0, C.at<float>(L.mapb), L.ldm, L.NM, C.mx(MX_MAP), C.at<float>(L.de1), ENC_H, ENC_H,
+                  C.mx(MX_DE1));
+  return 2;
+}
+
+void encoder_segments(const Ctx& C, SegBuilder& SB, int phase) {
+  const Lay& L = C.L;
+  seg_w(C, SB, W_E0, IE0, L.NM, phase);
+  SB.add(C.gB(IE0), C.at<float>(L.cse1), 1, ENC_H, 0, L.MT, ENC_H);
+  seg_w(C, SB, W_E2, IE2, ENC_H, phase);
+  SB.add(C.gB(IE2), C.at<float>(L.csemb), 1, L.E, 0, L.MT, L.E);
+}
+
 void adapt_segments(const Ctx& C, SegBuilder& SB, int phase) {
   const Lay& L = C.L;
   const int P = L.P, as = adapt_stride(P);
   const float* ap = C.at<float>(L.apart);
-  seg_w(C, SB, W_A0, IA0, L.H, phase);
+  seg_first(C, SB, W_A0, IA0, phase);
   SB.add(C.gB(IA0), C.at<float>(L.cs1a), 1, HA1, 0, L.MT, HA1);
   seg_w(C, SB, W_A2, IA2, HA1, phase);
   SB.add(C.gB(IA2), ap + P * 128 + P, 1, HA2, 0, L.HB, as);
@@ -1664,7 +1909,7 @@ int grad_phase0(const Ctx& C) {
   const go1_ppo_bufs* b = C.b;
   const int H = L.H, P = L.P;
   if (!b->obs_history || !b->privileged_obs || !b->actions || !b->values || !b->advantages || !b->returns ||
-      !b->actions_log_prob || !b->mu || !b->sigma || !b->idx || b->hist_ld < H)
+      !b->actions_log_prob || !b->mu || !b->sigma || !b->idx || b->hist_ld < L.Hs)
     return fail(GO1_PPO_E_ARG, "go1_ppo_grad: storage tensors and idx are required");
   int rc;
   // the mini-batch rows (the max slots were cleared by the previous step's finalize_kernel, or are fresh)
@@ -1691,9 +1936,23 @@ int grad_phase0(const Ctx& C) {
     ga.G = G;
     ga.B = Bb;
     ga.mx = C.mx(MX_G);
-    hipLaunchKernelGGL(gather_kernel, dim3(std::min(cdiv(L.M, 16), GATHER_BLOCKS_MAX)), dim3(256), 0, C.s, ga);
+    const dim3 grid(std::min(cdiv(L.M, 16), GATHER_BLOCKS_MAX));
+    if (L.enc) {
+      ga.E = L.E;
+      ga.S = L.SC;
+      ga.foff = L.foff;
+      ga.NM = L.NM;
+      ga.ldm = L.ldm;
+      ga.Mp = C.at<float>(L.mapb);
+      ga.mxmap = C.mx(MX_MAP);
+      hipLaunchKernelGGL(gather_kernel<true>, grid, dim3(256), 0, C.s, ga);
+    } else {
+      hipLaunchKernelGGL(gather_kernel<false>, grid, dim3(256), 0, C.s, ga);
+    }
     PPO_TRY(hipGetLastError());
   }
+  // ---- forward: the encoder on the last frame's map (ppo_cse_cnn: process_obs_history), once for the three heads
+  if (L.enc && (rc = encoder_forward(C))) return rc;
   float *a1a = C.at<float>(L.a1a);
   float *p1 = C.at<float>(L.p1), *p2 = C.at<float>(L.p2), *p3 = C.at<float>(L.p3);
   float *c1 = C.at<float>(L.c1), *c2 = C.at<float>(L.c2), *c3 = C.at<float>(L.c3);
@@ -1760,18 +2019,44 @@ int grad_phase0(const Ctx& C) {
   hipLaunchKernelGGL(adapt_kernel<2>, dim3(L.HB), dim3(256), 0, C.s, AD);
   PPO_TRY(hipGetLastError());
   if ((rc = adapt_backward_l2(C))) return rc;
+  // ---- the embedding's gradient from the three first layers, then the encoder's hidden layer's
+  if (L.enc) {
+    float *tp = C.at<float>(L.tp), *tc = C.at<float>(L.tc), *ta = C.at<float>(L.ta);
+    const float* zb = C.at<float>(L.zbias);
+    const int E = L.E;
+    XwProb pa = xw_prob(C, d1p, H1, H1, C.mx(MX_D1P), W_P0, true, E, zb, nullptr, 0, tp, E, nullptr, nullptr);
+    XwProb pc = xw_prob(C, d1c, H1, H1, C.mx(MX_D1C), W_C0, true, E, zb, nullptr, 0, tc, E, nullptr, nullptr);
+    if ((rc = launch_xw(C, EPI_LIN, pa, &pc))) return rc;
+    pa = xw_prob(C, d1a, HA1, HA1, C.mx(MX_D1A), W_A0, true, E, zb, nullptr, 0, ta, E, nullptr, nullptr);
+    if ((rc = launch_xw(C, EPI_LIN, pa, nullptr))) return rc;
+    EmbArgs ea{};
+    ea.tp = tp;
+    ea.tc = tc;
+    ea.ta = ta;
+    ea.emb = G;
+    ea.lde = L.ldg;
+    ea.demb = C.at<float>(L.demb);
+    ea.colsum = C.at<float>(L.csemb);
+    ea.dmax = C.mx(MX_DEMB);
+    ea.M = L.M;
+    ea.E = E;
+    hipLaunchKernelGGL(embgrad_kernel, dim3(L.MT, E / TB), dim3(256), 0, C.s, ea);
+    PPO_TRY(hipGetLastError());
+    if ((rc = encoder_backward(C))) return rc;
+  }
   // ---- weight gradients of the GEMM layers, one grouped launch
   {
-    WgProb ps[8];
+    WgProb ps[MAX_WG];
     ps[0] = wg_prob(C, W_P0, G, L.ldg, H + P, C.mx(MX_G), d1p, H1, H1, C.mx(MX_D1P), C.mx(MX_LAT));
     ps[1] = wg_prob(C, W_C0, G, L.ldg, H + 2 * P, C.mx(MX_G), d1c, H1, H1, C.mx(MX_D1C), C.mx(MX_LAT));
     ps[2] = wg_prob(C, W_P2, p1, H1, H1, C.mx(MX_P1), d2p, H2, H2, C.mx(MX_D2P));
     ps[3] = wg_prob(C, W_C2, c1, H1, H1, C.mx(MX_C1), d2c, H2, H2, C.mx(MX_D2C));
     ps[4] = wg_prob(C, W_P4, p2, H2, H2, C.mx(MX_P2), d3p, H3, H3, C.mx(MX_D3P));
     ps[5] = wg_prob(C, W_C4, c2, H2, H2, C.mx(MX_C2), d3c, H3, H3, C.mx(MX_D3C));
-    ps[6] = wg_prob(C, W_A0, G, L.ldg, H, C.mx(MX_G), d1a, HA1, HA1, C.mx(MX_D1A));
+    ps[6] = wg_prob(C, W_A0, G, L.ldg, H, C.mx(MX_G), d1a, HA1, HA1, C.mx(MX_D1A), L.enc ? C.mx(MX_LAT) : nullptr);
     ps[7] = wg_prob(C, W_A2, a1a, HA1, HA1, C.mx(MX_A1A), d2a, HA2, HA2, C.mx(MX_D2A));
-    if ((rc = launch_wg(C, ps, 8, 0))) return rc;
+    const int np = 8 + (L.enc ? encoder_wg(C, ps + 8) : 0);
+    if ((rc = launch_wg(C, ps, np, 0))) return rc;
   }
   // ---- partials -> flat gradient (+ aux: surrogate, value, KL sums)
   SegBuilder SB;
@@ -1780,8 +2065,9 @@ int grad_phase0(const Ctx& C) {
   const int o_db4p = A * 128, o_db3p = o_db4p + A, o_dW4c = o_db3p + 128, o_db4c = o_dW4c + 128, o_db3c = o_db4c + 1,
             o_dstd = o_db3c + 128, o_loss = o_dstd + A;
   SB.add(b->grads, hp + o_loss, 1, 3, 0, L.HB, hs);
+  if (L.enc) encoder_segments(C, SB, 0);
   adapt_segments(C, SB, 0);
-  seg_w(C, SB, W_P0, IP0, H + P, 0);
+  seg_first(C, SB, W_P0, IP0, 0);
   SB.add(C.gB(IP0), C.at<float>(L.cs1p), 1, H1, 0, L.MT, H1);
   seg_w(C, SB, W_P2, IP2, H1, 0);
   SB.add(C.gB(IP2), C.at<float>(L.cs2p), 1, H2, 0, L.MT, H2);
@@ -1789,12 +2075,7 @@ int grad_phase0(const Ctx& C) {
   SB.add(C.gB(IP4), hp + o_db3p, 1, H3, 0, L.HB, hs);
   SB.add(C.gW(IP6), hp, 1, A * 128, 0, L.HB, hs);
   SB.add(C.gB(IP6), hp + o_db4p, 1, A, 0, L.HB, hs);
-  {  // the critic's first layer: G's hist columns, then its priv columns (the latent columns' gradient is dropped)
-    const int kpad = cdiv(H + 2 * P, TB) * TB;
-    const float* wp = C.at<float>(L.wpart[W_C0]);
-    SB.add(C.gW(IC0), wp, H1, H, kpad, L.S[0], L.wpart_stride[W_C0], H + P);
-    SB.add(C.gW(IC0) + H, wp + H + P, H1, P, kpad, L.S[0], L.wpart_stride[W_C0], H + P);
-  }
+  seg_first(C, SB, W_C0, IC0, 0);  // G's hist columns, then its priv columns
   SB.add(C.gB(IC0), C.at<float>(L.cs1c), 1, H1, 0, L.MT, H1);
   seg_w(C, SB, W_C2, IC2, H1, 0);
   SB.add(C.gB(IC2), C.at<float>(L.cs2c), 1, H2, 0, L.MT, H2);
@@ -1811,23 +2092,37 @@ int grad_phase1(const Ctx& C) {
   const go1_ppo_bufs* b = C.b;
   const int P = L.P;
   int rc;
-  // the gathered rows G are this mini-batch's (phase 0); the maxima phase 1 recomputes were cleared by step 0
+  // the gathered rows G are this mini-batch's (phase 0); the maxima phase 1 recomputes were cleared by step 0.
+  // The encoder's weights moved in step 0: the embedding columns of G are computed again
+  if (L.enc && (rc = encoder_forward(C))) return rc;
   if ((rc = adapt_forward(C))) return rc;
   AdaptArgs AD = adapt_args(C);
   hipLaunchKernelGGL(adapt_kernel<1>, dim3(L.HB), dim3(256), 0, C.s, AD);
   PPO_TRY(hipGetLastError());
   if ((rc = adapt_backward_l2(C))) return rc;
+  if (L.enc) {  // d emb = (W_A0[:, emb]^T delta1a) * ELU'(emb): the adaptation module is the only path here
+    if ((rc = launch_xw(C, EPI_DELU,
+                        xw_prob(C, C.at<float>(L.d1a), HA1, HA1, C.mx(MX_D1A), W_A0, true, L.E, nullptr,
+                                C.at<float>(L.G), L.ldg, C.at<float>(L.demb), L.E, C.mx(MX_DEMB),
+                                C.at<float>(L.csemb)),
+                        nullptr)))
+      return rc;
+    if ((rc = encoder_backward(C))) return rc;
+  }
   {
-    WgProb ps[2];
-    ps[0] = wg_prob(C, W_A0, C.at<float>(L.G), L.ldg, L.H, C.mx(MX_G), C.at<float>(L.d1a), HA1, HA1, C.mx(MX_D1A));
+    WgProb ps[4];
+    ps[0] = wg_prob(C, W_A0, C.at<float>(L.G), L.ldg, L.H, C.mx(MX_G), C.at<float>(L.d1a), HA1, HA1, C.mx(MX_D1A),
+                    L.enc ? C.mx(MX_LAT) : nullptr);
     ps[1] = wg_prob(C, W_A2, C.at<float>(L.a1a), HA1, HA1, C.mx(MX_A1A), C.at<float>(L.d2a), HA2, HA2,
                     C.mx(MX_D2A));
-    if ((rc = launch_wg(C, ps, 2, 1))) return rc;
+    const int np = 2 + (L.enc ? encoder_wg(C, ps + 2) : 0);
+    if ((rc = launch_wg(C, ps, np, 1))) return rc;
   }
   SegBuilder SB;
   const int as = adapt_stride(P);
   const float* ap = C.at<float>(L.apart);
   SB.add(b->grads + 3, ap + P * 128 + P + 128, 1, 2, 0, L.HB, as);  // aux[3], aux[4]: adaptation loss sums
+  if (L.enc) encoder_segments(C, SB, 1);
   adapt_segments(C, SB, 1);
   return launch_reduce(C, SB);
 }
@@ -1857,14 +2152,19 @@ int step_phase(const Ctx& C, int phase) {
   F.scal = C.at<float>(L.scal) + 8 * phase;
   // phase 0 clears the maxima phase 1 recomputes and the weight maxima of the pack that follows; phase 1 clears
   // every activation / gradient maximum (the next mini-batch) and the adaptation weights' maxima
+  for (int i = 0; i < 6; ++i) F.zero[i] = C.mx(MX_G), F.nz[i] = 0;
   if (phase == 0) {
     F.zero[0] = C.mx(MX_A1A), F.nz[0] = 2;
     F.zero[1] = C.mx(MX_D2A), F.nz[1] = 2;
-    F.zero[2] = C.at<uint32_t>(L.wmax), F.nz[2] = (int)W_N;
+    F.zero[2] = C.at<uint32_t>(L.wmax), F.nz[2] = L.nW;
+    if (L.enc) {  // the embedding (MX_LAT), the encoder's hidden layer and the two deltas are computed again
+      F.zero[3] = C.mx(MX_LAT), F.nz[3] = 1;
+      F.zero[4] = C.mx(MX_E1), F.nz[4] = 3;
+    }
   } else {
     F.zero[0] = C.mx(MX_G), F.nz[0] = (int)MX_N;
-    F.zero[1] = C.at<uint32_t>(L.wmax), F.nz[1] = 2;
-    F.zero[2] = C.at<uint32_t>(L.wmax), F.nz[2] = 0;
+    F.zero[1] = C.at<uint32_t>(L.wmax) + W_A0, F.nz[1] = 2;
+    if (L.enc) F.zero[2] = C.at<uint32_t>(L.wmax) + W_E0, F.nz[2] = 2;
   }
   hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, C.s, F);
   PPO_TRY(hipGetLastError());

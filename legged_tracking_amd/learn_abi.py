@@ -7,12 +7,15 @@ go1_ppo_abi_sizes of the compiled libraries.
 import ctypes as C
 
 GO1_ROLLOUT_ABI_VERSION = 1
-GO1_PPO_ABI_VERSION = 1
+GO1_PPO_ABI_VERSION = 2
 GO1_POLICY_LAYERS = 11
 GO1_PPO_AUX = 8
 GO1_ENCODER_LAYERS = 3
 GO1_ENC_MLP, GO1_ENC_CNN = 0, 1
 GO1_ENC_MAX_EMBED = 512
+GO1_PPO_ENC_NONE, GO1_PPO_ENC_MLP = 0, 1  # go1_ppo_dims.enc_mode
+GO1_PPO_ENC_HIDDEN = 256
+GO1_PPO_ENC_MAX_MAP = 4096
 
 P = C.c_void_p
 I32 = C.c_int32
@@ -48,7 +51,9 @@ class EncoderArgs(C.Structure):  # go1_encoder_args
 
 
 class PPODims(C.Structure):  # go1_ppo_dims
-    _fields_ = [("hist", I32), ("priv", I32), ("actions", I32), ("mb", I32), ("rows", I64)]
+    _fields_ = [("hist", I32), ("priv", I32), ("actions", I32), ("mb", I32), ("rows", I64),
+                # the height-map encoder in front of the heads (ABI 2); all zero: the plain module
+                ("enc_mode", I32), ("num_obs", I32), ("n_map", I32), ("n_embed", I32)]
 
 
 class PPOBufs(C.Structure):  # go1_ppo_bufs
@@ -91,6 +96,8 @@ POLICY_LINEARS = tuple(("adaptation_module", i) for i in (0, 2, 4)) + \
                  tuple(("actor_body", i) for i in (0, 2, 4, 6)) + tuple(("critic_body", i) for i in (0, 2, 4, 6))
 assert len(POLICY_LINEARS) == GO1_POLICY_LAYERS
 N_ADAPT_LINEARS = 3
+# the MLP height-map encoder's Linear layers (rollout_cnn.HeightMapEncoder.model), in front of the heads
+ENCODER_LINEARS = (("height_map_encoder.model", 0), ("height_map_encoder.model", 2))
 
 
 def policy_linears(ac):

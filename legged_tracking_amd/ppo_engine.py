@@ -28,6 +28,11 @@ NAUX = LA.GO1_PPO_AUX
 # state_dict order of the supported ActorCritic, as the engine lays out its flat buffers (go1_ppo.h)
 PARAM_NAMES = [f"{seq}.{i}.{k}" for seq, i in LA.POLICY_LINEARS for k in ("weight", "bias")] + ["std"]
 N_ADAPT_TENSORS = 2 * LA.N_ADAPT_LINEARS
+# the MLP height-map encoder's parameters (rollout_cnn.ActorCritic): they lead the engine's flat buffers, and the
+# adaptation optimizer's slice is encoder + adaptation module (ppo_cse_cnn/ppo.py:170-190 back-propagates the
+# adaptation loss through process_obs_history)
+ENC_PARAM_NAMES = [f"{seq}.{i}.{k}" for seq, i in LA.ENCODER_LINEARS for k in ("weight", "bias")]
+ENC_EMBEDDINGS = (128, 256, 384, 512)
 
 _lib = None
 
@@ -49,21 +54,49 @@ def load_library(path=None):
     return l
 
 
-def supported(ac):
-    """The engine's architecture: AC_Args' default widths, ELU, latent 1..8, actions 1..16, no decoder."""
-    try:
-        a, p, c = ac.adaptation_module, ac.actor_body, ac.critic_body
-        names = [n for n, _ in ac.named_parameters()]
-    except AttributeError:
-        return False
+def _elu(mods):
+    return all(isinstance(m, torch.nn.ELU) and m.alpha == 1.0 for m in mods)
+
+
+def _heads_supported(ac, names, width):
+    """The three heads on an input of `width` columns: AC_Args' default widths, ELU, latent 1..8, actions 1..16."""
+    a, p, c = ac.adaptation_module, ac.actor_body, ac.critic_body
     if sorted(names) != sorted(PARAM_NAMES) or len(a) != 5 or len(p) != 7 or len(c) != 7:
         return False
     lin = LA.policy_linears(ac)
     npv, na = ac.num_privileged_obs, lin[6].out_features
-    ok = [tuple(m.weight.shape) for m in lin] == LA.policy_shapes(ac.num_obs_history, npv, na)
+    ok = [tuple(m.weight.shape) for m in lin] == LA.policy_shapes(width, npv, na)
     acts = [m for seq in (a, p, c) for m in seq if not isinstance(m, torch.nn.Linear)]
-    return (ok and 1 <= npv <= 8 and 1 <= na <= 16 and all(isinstance(m, torch.nn.ELU) and m.alpha == 1.0
-                                                            for m in acts))
+    return ok and 1 <= npv <= 8 and 1 <= na <= 16 and _elu(acts)
+
+
+def supported(ac):
+    """The engine's architecture: AC_Args' default widths, ELU, latent 1..8, actions 1..16, no decoder."""
+    try:
+        return _heads_supported(ac, [n for n, _ in ac.named_parameters()], ac.num_obs_history)
+    except AttributeError:
+        return False
+
+
+def encoder_supported(ac):
+    """The engine's encoder architecture (go1_ppo_dims.enc_mode 1): rollout_cnn.ActorCritic with the MLP encoder
+    (use_cnn False; map -> 256 -> E, ELU, E in ENC_EMBEDDINGS, a map of 1..4096 values), whole frames in the
+    history, and the supported heads on policy_input_dim.  supported() stays False for this module: whether its
+    update runs on the engine is rollout_cnn.ENGINE_DEFAULT / GO1_PPO_ENCODER_ENGINE's decision."""
+    try:
+        if ac.use_cnn or not isinstance(ac.recurrent_latent_embedding, torch.nn.Identity):
+            return False
+        names = [n for n, _ in ac.named_parameters()]
+        model, n_map, E = ac.height_map_encoder.model, ac.num_map, ac.cnn_num_embedding
+        if len(model) != 4 or sorted(n for n in names if n not in PARAM_NAMES) != sorted(ENC_PARAM_NAMES):
+            return False
+        shapes = [tuple(model[i].weight.shape) for i in (0, 2)]
+        enc = (shapes == [(LA.GO1_PPO_ENC_HIDDEN, n_map), (E, LA.GO1_PPO_ENC_HIDDEN)] and E in ENC_EMBEDDINGS
+               and 1 <= n_map <= min(LA.GO1_PPO_ENC_MAX_MAP, ac.num_obs) and _elu([model[1], model[3]])
+               and ac.num_obs_history % ac.num_obs == 0 and ac.policy_input_dim == 2 * (ac.num_obs - n_map) + E)
+        return enc and _heads_supported(ac, [n for n in names if n in PARAM_NAMES], ac.policy_input_dim)
+    except (AttributeError, IndexError, TypeError):
+        return False
 
 
 class PPOEngine:
@@ -76,8 +109,15 @@ class PPOEngine:
         self.device = next(ac.parameters()).device
         self.hist, self.priv = ac.num_obs_history, ac.num_privileged_obs
         self.na = ac.actor_body[6].out_features
+        # the encoder module (encoder_supported): its parameters lead the flat buffers and the phase-1 slice
+        self.enc_dims = {}
+        if encoder_supported(ac):
+            self.enc_dims = dict(enc_mode=LA.GO1_PPO_ENC_MLP, num_obs=ac.num_obs, n_map=ac.num_map,
+                                 n_embed=ac.cnn_num_embedding)
+        self.names = (ENC_PARAM_NAMES if self.enc_dims else []) + PARAM_NAMES
+        self.n_adapt_tensors = N_ADAPT_TENSORS + (len(ENC_PARAM_NAMES) if self.enc_dims else 0)
         self._stream = native.raw_stream_of(self.device)
-        dims = LA.PPODims(hist=self.hist, priv=self.priv, actions=self.na, mb=1, rows=1)
+        dims = LA.PPODims(hist=self.hist, priv=self.priv, actions=self.na, mb=1, rows=1, **self.enc_dims)
         tot, ad = C.c_int64(), C.c_int64()
         native.check(self.lib, self.lib.go1_ppo_param_count(C.byref(dims), C.byref(tot), C.byref(ad)))
         self.n_total, self.n_adapt = tot.value, ad.value
@@ -85,14 +125,14 @@ class PPOEngine:
         sd = dict(ac.named_parameters())
         self.offsets = {}
         off = 0
-        for name in PARAM_NAMES:
+        for name in self.names:
             self.offsets[name] = off
             off += sd[name].numel()
-        if off != self.n_total or self.offsets[PARAM_NAMES[N_ADAPT_TENSORS]] != self.n_adapt:
+        if off != self.n_total or self.offsets[self.names[self.n_adapt_tensors]] != self.n_adapt:
             raise native.NativeError("PPO engine: parameter layout mismatch between the module and go1_ppo.h")
         # flat buffers; the module's parameters become views into `params`
         self.params = torch.empty(self.n_total, dtype=torch.float32, device=dev)
-        for name in PARAM_NAMES:
+        for name in self.names:
             p, o = sd[name], self.offsets[name]
             self.params[o:o + p.numel()].copy_(p.detach().reshape(-1))
             p.data = self.params[o:o + p.numel()].view_as(p)
@@ -119,7 +159,7 @@ class PPOEngine:
     # ------------------------------------------------------------------ helpers
     def _param_list(self, adaptation_only=False):
         sd = dict(self.alg.actor_critic.named_parameters())
-        names = PARAM_NAMES[:N_ADAPT_TENSORS] if adaptation_only else PARAM_NAMES
+        names = self.names[:self.n_adapt_tensors] if adaptation_only else self.names
         return [(n, sd[n]) for n in names]
 
     def _views(self, flat, adaptation_only=False):
@@ -212,7 +252,7 @@ class PPOEngine:
 
     def _bind(self, st, mb):
         rows = st.num_envs * st.num_transitions_per_env
-        dims = LA.PPODims(hist=self.hist, priv=self.priv, actions=self.na, mb=mb, rows=rows)
+        dims = LA.PPODims(hist=self.hist, priv=self.priv, actions=self.na, mb=mb, rows=rows, **self.enc_dims)
         nb = C.c_int64()
         native.check(self.lib, self.lib.go1_ppo_workspace_bytes(C.byref(dims), C.byref(nb)))
         if self.work is None or self.work.numel() < nb.value:

@@ -547,8 +547,10 @@ class PPO:
         # captured once into a HIP graph and replayed for every later mini-batch (GO1_PPO_GRAPH=0: eager):
         # it is ~150 small launches whose host issue left the GPU idle between them.  One rank only (the
         # gradient all-reduce stays eager).
-        self._graph_on = (self._dev_lr and os.environ.get("GO1_PPO_GRAPH", "1") != "0"
-                          and getattr(actor_critic, "graph_capture", True))
+        # The engine's update is captured by GO1_PPO_GRAPH alone; `graph_capture` is the module's word on its torch
+        # update (rollout_cnn.ActorCritic: eager).
+        self._engine_graph = self._dev_lr and os.environ.get("GO1_PPO_GRAPH", "1") != "0"
+        self._graph_on = self._engine_graph and getattr(actor_critic, "graph_capture", True)
         self._graph = self._graph_key = None
         self._graph_warm = 0
         self._graph_idx = self._graph_acc = self._graph_draw = None  # static buffers of the captured step
@@ -834,11 +836,17 @@ class PPO:
 
     def _engine_on(self):
         """The hand-written HIP update (ppo_engine.PPOEngine, csrc/ppo_update.hip) on the GPU for the default
-        architecture; GO1_PPO_ENGINE=0 selects the torch autograd update (A/B)."""
+        architecture; GO1_PPO_ENGINE=0 selects the torch autograd update (A/B).  The height-map encoder module
+        runs on it where rollout_cnn.encoder_engine_on says so (ENGINE_DEFAULT, GO1_PPO_ENCODER_ENGINE)."""
         if torch.device(self.device).type != "cuda" or os.environ.get("GO1_PPO_ENGINE", "1") == "0":
             return False
         from . import ppo_engine
-        return ppo_engine.supported(self.actor_critic)
+        if ppo_engine.supported(self.actor_critic):
+            return True
+        if not ppo_engine.encoder_supported(self.actor_critic):
+            return False
+        from . import rollout_cnn
+        return rollout_cnn.encoder_engine_on(self.actor_critic)
 
     def _set_lr(self, lr):
         """The learning rate of PPO.optimizer, everywhere it is kept: the attribute, the param groups (a device
@@ -862,7 +870,7 @@ class PPO:
             if self._engine is None:
                 self._engine = ppo_engine.PPOEngine(self)
             sums, lr = self._engine.update(A, A.num_mini_batches, A.num_learning_epochs, _world(),
-                                           use_graph=self._graph_on,
+                                           use_graph=self._engine_graph,
                                            split=os.environ.get("GO1_PPO_SPLIT", "0") == "1")
             self._set_lr(lr)
         else:

@@ -21,10 +21,13 @@ MLPs on policy_input in place of the history.
 
 MI355X mapping: the rollout's forward is two HIP launches (FusedEncoderPolicy): go1_heightmap_encode
 (csrc/encoder.hip) writes policy_input, go1_policy_forward (csrc/rollout.hip) runs the three heads on it.  The
-PPO update of this module runs on torch autograd, eagerly (ppo_engine.supported refuses its parameter names,
-and the mini-batch step is not captured into a HIP graph).
+PPO update of this module runs on torch autograd, eagerly, by default (ppo_engine.supported refuses its parameter
+names, and that mini-batch step is not captured into a HIP graph).  With the MLP encoder it also runs on the HIP
+update engine (csrc/ppo_update.hip, go1_ppo_dims.enc_mode 1: one encoder pass on the last frame, captured into a
+HIP graph), switched by ENGINE_DEFAULT / GO1_PPO_ENCODER_ENGINE.
 """
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -39,6 +42,18 @@ ENC_HIDDEN = 256     # the MLP encoder's hidden width (actor_critic.py:49)
 # Which encoder modes take FusedEncoderPolicy in the rollout by default: those whose encode + policy launches
 # beat the module's torch eager act + evaluate at 4096 envs (tools/encoder_kernel_time.py).
 FUSED_DEFAULT = {"mlp": True, "cnn": True}
+# Which encoder modes take the HIP update engine (ppo_engine.PPOEngine with go1_ppo_dims.enc_mode) in PPO.update
+# by default.  The engine has the MLP encoder (ppo_engine.encoder_supported); the CNN's backward is not built.
+# GO1_PPO_ENCODER_ENGINE=1 / 0 overrides the default for a run; GO1_PPO_ENGINE=0 switches every engine off.
+ENGINE_DEFAULT = {"mlp": False, "cnn": False}
+
+
+def encoder_engine_on(ac):
+    """The switch PPO._engine_on consults for this module (the architecture check is ppo_engine's)."""
+    env = os.environ.get("GO1_PPO_ENCODER_ENGINE")
+    if env in ("0", "1"):
+        return env == "1"
+    return ENGINE_DEFAULT["cnn" if ac.use_cnn else "mlp"]
 
 
 class AC_Args(R.AC_Args):
