@@ -1,5 +1,6 @@
 /*
- * go1_ppo.h -- C ABI of the MI355X PPO update engine (legged_tracking_amd/csrc/ppo_update.hip).
+ * go1_ppo.h -- C ABI of the MI355X PPO update engine (legged_tracking_amd/csrc/ppo_update.hip: the launch chain
+ * and these entry points; its kernels and the workspace layout in the csrc/ppo_*.h headers it includes).
  *
  * Replaces, for the update half of the hot path (go1_gym_learn/ppo_cse/ppo.py:98-206, one mini-batch of
  * PPO.update), the torch autograd / hipBLASLt / torch.optim pipeline:

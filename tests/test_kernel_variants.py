@@ -43,8 +43,11 @@ def test_only_diagnostic_switches_remain():
     stray = {c for c in conds if c.startswith("GO1_") and c not in allowed and not c.startswith("GO1_ABL_")}
     assert not stray, f"variant switches outside the diagnostic set: {sorted(stray)}"
     # the learn libraries and their headers: the two stamp builds and the header guards, nothing else
-    learn = "".join(open(f).read() for f in (ROLLOUT_SRC, PPO_SRC, os.path.join(INC, "go1_rollout.h"),
-                                             os.path.join(INC, "go1_ppo.h")))
+    # (ppo_update.hip with every csrc header it reaches: a switch in one of its parts is a switch in the engine)
+    ppo = [f for f in B.include_closure([PPO_SRC]) if os.path.dirname(f) == CSRC]
+    assert len(ppo) > 1, ppo
+    learn = "".join(open(f).read() for f in [ROLLOUT_SRC, *ppo, os.path.join(INC, "go1_rollout.h"),
+                                             os.path.join(INC, "go1_ppo.h")])
     conds = set(re.findall(r"#\s*(?:if|ifdef|ifndef|elif)\s+!?\s*(?:defined\s*\(?\s*)?(\w+)", learn))
     allowed = {"GO1_POLICY_STAMPS", "PPO_STAMPS", "GO1_ROLLOUT_H", "GO1_PPO_H"}
     stray = {c for c in conds if c.startswith(("GO1_", "PPO_")) and c not in allowed}

@@ -11,7 +11,7 @@ encoder's xw<DELU> launches of both phases, the ten-problem grouped wgrad, the 3
 layers' column blocks mapped back, finalize_kernel's wider clear lists, Adam and the re-pack over the wider phase-1
 slice (encoder + adaptation module).
 
-Data (`_Case`): tests/test_ppo_engine_grad.py's recipe (its _Case docstring) from the f64 forward of this module;
+Data (tests/ppo_cases.py's `_Case`): tests/test_ppo_engine_grad.py's recipe from the f64 forward of this module;
 history frames of N(0, 1) scalars and U(-5, 5) map values (tests/cnn_cases.py), biases and std off their initial
 values.  Shapes (map, E, frames, priv, actions, mb):
     production      2x21x11  256  2   2  12  37     production widths, the frame offset, a ragged tile
@@ -38,27 +38,30 @@ buffer's largest value, fresh and from step 999; after step(1) the actor, the cr
 the encoder has moved.  Determinism: two fresh engines agree to the bit; hyper.world = 2 with the gradient doubled
 in place is world 1 to the bit.
 
-Single-line mutations of csrc/ppo_update.hip these tests were checked against (each fails
-test_gradients_and_loss_sums_against_f64 on every shape unless noted): the critic's term dropped from embgrad_kernel's
-sum; embgrad_kernel's ELU' taken from t_p instead of the embedding; delta e1's ELU' taken from a1a instead of e1;
-phase 1 without its encoder forward (phase 0's embedding reused); the gather's frame offset 0 (fails production and
-window, the two-frame shapes); the first layers' gradient segment covering one copy of the scalars only.
+Single-line mutations of the engine's source these tests were checked against (each fails
+test_gradients_and_loss_sums_against_f64 on every shape unless noted).  In embgrad_kernel (csrc/ppo_gather.h): the
+critic's term dropped from its sum; its ELU' taken from t_p instead of the embedding.  In csrc/ppo_layout.h: delta
+e1's ELU' taken from a1a instead of e1 (the output of the W_E0 row); the first layers' gradient segment covering one
+copy of the scalars only (Ctx::segs).  In csrc/ppo_update.hip: phase 1 without its encoder forward (phase 0's
+embedding reused); the gather's frame offset 0 (gather_args; fails production and window, the two-frame shapes).
 """
+import functools
+
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
-from legged_tracking_amd import ppo_engine as PE, rollout as R, rollout_cnn as RC  # noqa: E402
-from tests import ppo_ref_cnn as ref  # noqa: E402
-from tests.test_ppo_engine_grad import (DELTAS, FLOOR, KL0, VOFFS, _args, _check_branches, _errs, _step_check,  # noqa: E402
-                                        _torch_adam)
+from legged_tracking_amd import ppo_engine as PE  # noqa: E402
+from tests import ppo_cases, ppo_ref_cnn as ref  # noqa: E402
+from tests.ppo_cases import DEV, _Case, _args  # noqa: E402
+from tests.test_ppo_engine_grad import _check_branches, _step_check, _torch_adam  # noqa: E402
 
-DEV = "cuda:0"
 NAUX = PE.NAUX
 K_GRAD = 32.0  # the module docstring
 NAMES = ref.NAMES
 N1 = ref.N_PHASE1_TENSORS
+_compare = functools.partial(ppo_cases._compare, k_grad=K_GRAD, show="[enc-grad]")
 
 SHAPES = {
     # name: (map shape, E, scalars, frames, priv, actions, mb, window)
@@ -70,120 +73,9 @@ SHAPES = {
 }
 
 
-class _Case:
-    """A fresh engine on a storage whose mini-batch rows populate every branch of the loss (tests/test_ppo_engine_grad.py's
-    _Case, for the encoder module)."""
-
-    def __init__(self, shape, E, S, frames, priv, na, mb, window=0, seed=0):
-        import math
-        import types
-        n_map = int(np.prod(shape))
-        num_obs = S + n_map
-        hist = frames * num_obs
-        g = torch.Generator().manual_seed(1000 * seed + hist + 7 * priv + 13 * na + mb + E)
-        self.priv, self.na, self.mb = priv, na, mb
-        rows = self.rows = mb + max(3, mb // 7)
-        torch.manual_seed(seed + 5)
-        args = type("A", (RC.AC_Args,), dict(height_map_shape=shape, cnn_num_embedding=E))
-        ac = RC.ActorCritic(num_obs, priv, hist, na, ac_args=args)
-        assert PE.encoder_supported(ac)
-        with torch.no_grad():  # biases and std off their initial 0 / 1, so that each one matters
-            for n, p in ac.named_parameters():
-                if n.endswith("bias"):
-                    p.add_(0.05 * torch.randn(p.shape, generator=g))
-            ac.std.copy_(0.6 + 0.8 * torch.rand(na, generator=g))
-        self.alg = alg = R.PPO(ac, device=DEV)
-        perm = torch.randperm(rows, generator=g)
-        at = int((perm == rows - 1).nonzero())
-        if at >= mb:  # the last storage row is part of the mini-batch
-            perm[[mb // 2, at]] = perm[[at, mb // 2]]
-        self.idx = idx = perm[:mb].to(DEV)
-        assert int(idx.max()) == rows - 1 and rows > mb
-        fr = torch.randn(rows, frames, num_obs, generator=g)
-        fr[:, :, S:] = torch.rand(rows, frames, n_map, generator=g) * 10.0 - 5.0
-        wide = torch.randn(1, rows, hist + (350 if window else 0), generator=g)
-        wide[0, :, window:window + hist] = fr.reshape(rows, hist)
-        wide = wide.to(DEV)
-        st = types.SimpleNamespace(num_envs=rows, num_transitions_per_env=1)
-        st.observation_histories = wide[:, :, window:window + hist] if window else wide
-        st.privileged_observations = (0.5 * torch.randn(1, rows, priv, generator=g)).to(DEV)
-        for k, w in (("actions", na), ("mu", na), ("values", 1), ("advantages", 1), ("returns", 1),
-                     ("actions_log_prob", 1)):
-            setattr(st, k, torch.randn(1, rows, w, generator=g).to(DEV))
-        st.sigma = (0.5 + torch.rand(1, rows, na, generator=g)).to(DEV)
-        ac64 = ref.double_copy(alg.actor_critic)
-        m = torch.arange(mb)
-        with torch.no_grad():
-            h = st.observation_histories[0, idx].double()
-            pv = st.privileged_observations[0, idx].double()
-            x = ac64.process_obs_history(h)
-            mu64 = ac64.actor_body(torch.cat((x, ac64.adaptation_module(x)), -1))
-            v64 = ac64.critic_body(torch.cat((x, pv), -1))
-            std = ac64.std.detach()
-            z = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64).to(DEV)  # noqa: E731
-            actions = (mu64 + std * z(mb, na)).float()
-            logp64 = torch.distributions.Normal(mu64, std).log_prob(actions.double()).sum(-1, keepdim=True)
-            delta = torch.tensor(DELTAS, dtype=torch.float64)[m % 5].to(DEV)[:, None]
-            sign = torch.where(m % 2 == 0, 1.0, -1.0).double().to(DEV)[:, None]
-            big = torch.where((m % 4 == 3) | (m == mb - 1), 10.0, 1.0).double().to(DEV)[:, None]
-            adv = sign * big * (0.5 + z(mb, 1).abs())
-            voff = torch.tensor(VOFFS, dtype=torch.float64)[m % 4].to(DEV)[:, None]
-            flip = torch.where(torch.rand(mb, na, generator=g) < 0.5, -1.0, 1.0).double().to(DEV)
-            sig_old = std * (1.0 + 0.01 * torch.where(m % 2 == 0, 1.0, -1.0).double().to(DEV)[:, None])
-            sig_old = sig_old.expand(mb, na)
-            mu_old = mu64 + flip * std * math.sqrt(2.0 * KL0 / na)
-            for k, v in (("actions", actions), ("actions_log_prob", logp64 + delta), ("advantages", adv),
-                         ("values", v64 + voff), ("returns", v64 + z(mb, 1)), ("mu", mu_old), ("sigma", sig_old)):
-                getattr(st, k)[0, idx] = v.float()
-        self.storage = alg.storage = st
-        self.eng = PE.PPOEngine(alg)
-        assert self.eng.enc_dims and self.eng.names == NAMES
-        self.rows32 = ref.rows_of(st)
-        self.rows64 = ref.rows_of(st, torch.float64)
-
-    def start(self, world=1):
-        """_bind, _write_hyper, pack, idx: ready for grad(0).  Returns the hyper-parameter dict of the restatement."""
-        e = self.eng
-        e._bind(self.storage, self.mb)
-        if self.storage.observation_histories.stride(1) > self.storage.observation_histories.shape[2]:
-            assert e.bufs.hist_ld > e.hist  # the window reaches the engine as a strided view, not as a copy
-        e._write_hyper(R.PPO_Args, world)
-        e.pack()
-        e.idx.copy_(self.idx)
-        return ref.hyper_from_args(R.PPO_Args)
-
-    def ac64(self):
-        """The engine's current parameters as a float64 module."""
-        torch.cuda.synchronize()
-        return ref.double_copy(self.alg.actor_critic)
-
-    def split(self, flat_vec, phase1_only=False):
-        return list(self.eng._views(flat_vec, phase1_only).values())
-
-
 def _case(shape_name, seed=0):
-    return _Case(*SHAPES[shape_name], seed=seed)
-
-
-def _compare(tag, names, eng, yard, ref64, worst, row_terms):
-    """tests/test_ppo_engine_grad.py's _compare with this file's K_GRAD."""
-    bad = []
-    for n, a, y, r in zip(names, eng, yard, ref64):
-        assert float(r.double().abs().max()) > 0.0, (tag, n)
-        floors = [FLOOR, FLOOR]
-        if n in row_terms:
-            mag = row_terms[n].double().abs().sum(0).reshape(-1)
-            r1 = r.double().reshape(-1)
-            floors = [FLOOR * max(1.0, float(mag.max() / r1.abs().max())),
-                      FLOOR * max(1.0, float(mag.norm() / r1.norm()))]
-        for metric, ea, ey, fl in zip(("max", "l2"), _errs(a, r), _errs(y, r), floors):
-            ratio = max(ea, fl) / max(ey, fl)
-            print(f"[enc-grad] {tag}:{n}:{metric} engine {ea:.2e} yardstick {ey:.2e} ratio {ratio:.2f}")
-            if ratio > worst[0]:
-                worst[:] = [ratio, f"{tag}:{n}:{metric} engine {ea:.2e} yardstick {ey:.2e}"]
-            if not ratio <= K_GRAD:
-                bad.append((tag, n, metric, ea, ey))
-    return bad
+    shape, E, S, frames, priv, na, mb, window = SHAPES[shape_name]
+    return _Case(None, priv, na, mb, window, seed, encoder=(shape, E, S, frames))
 
 
 @pytest.mark.gpu

@@ -10,7 +10,7 @@ Kernels reached: gather_kernel (ragged mb, its grid-stride wrap, hist_ld > hist,
 head_kernel<12|16> (1, 12, 13, 16 actions, odd mb, the wrap), the EPI_DELU backward launches, the critic's
 two-segment first-layer gradient copy, reduce_kernel, norm_kernel, finalize_kernel, adam_kernel.
 
-Data (`_Case`): the stored quantities are built from the f64 forward of the same weights so that no row sits near a
+Data (`_Case`, tests/ppo_cases.py): the stored quantities are built from the f64 forward of the same weights so that no row sits near a
 clip edge in either precision and every branch of the loss holds >= 10 % of the rows (asserted from the f64 values):
 ratios exp(-delta), delta cycling over {-0.5, -0.1, 0, 0.1, 0.5} (1.65, 1.105, 1, 0.905, 0.61 against the clip
 [0.8, 1.2]); advantages of both signs, the last row of every group of 4 and of the mini-batch 10 x larger (a dropped
@@ -42,16 +42,17 @@ Measured (engine / yardstick): parameters 4.8e-8 / 4.8e-8 .. 5.9e-8 / 5.9e-8, ex
 finalize_kernel taking 1 - beta from the f32-rounded betas (exp_avg 4 ulp, exp_avg_sq 1.3e-5 relative off torch's);
 fixed in the kernel.
 
-Mutations of csrc/ppo_update.hip these tests were checked against (each fails the named test): invM from M + 1,
-tie weights 1, the value_loss_coef dropped from dV, the entropy term's sign, num_train = M * 4 / 5, the critic's
-priv-column copy from offset H (test_gradients_* / test_hyper_parameter_branches_*); inr with < (test_rows_exactly_on_the_clip_edge_*); gscale
-without / world (test_fresh_engines_*); bc2 without the square root (test_step_*).  The
+Mutations of the engine's source these tests were checked against (each fails the named test).  In head_kernel
+(csrc/ppo_heads.h): invM from M + 1, tie weights 1, the value_loss_coef dropped from dV, the entropy term's sign
+(test_gradients_* / test_hyper_parameter_branches_*); inr with < (test_rows_exactly_on_the_clip_edge_*).  In
+csrc/ppo_layout.h: num_train = M * 4 / 5 (make_layout), the critic's priv-column copy from offset H (Ctx::segs)
+(test_gradients_*).  In finalize_kernel (csrc/ppo_step.h): gscale without / world (test_fresh_engines_*); bc2 without
+the square root (test_step_*).  The
 head loop bound m < H.M instead of m < H.M + half computes the same values (the half-wave shuffles never cross the
 halves; the + half only keeps the wave's trip count uniform): no test can tell it apart.
 """
-import contextlib
+import functools
 import math
-import types
 
 import numpy as np
 import pytest
@@ -59,16 +60,12 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from legged_tracking_amd import ppo_engine as PE, rollout as R  # noqa: E402
-from tests import ppo_ref  # noqa: E402
+from tests import ppo_cases, ppo_ref  # noqa: E402
+from tests.ppo_cases import DELTAS, DEV, FLOOR, KL0, VOFFS, _Case, _args, _errs  # noqa: E402,F401
 
-DEV = "cuda:0"
 NAUX = PE.NAUX
 K_GRAD = 32.0  # the module docstring: measured worst ratio 8.55
-FLOOR = 2.0 ** -24
-
-DELTAS = (-0.5, -0.1, 0.0, 0.1, 0.5)
-VOFFS = (-0.5, -0.05, 0.05, 0.5)
-KL0 = 0.04  # the data's KL mean (plus actions * log(1 + 1e-5))
+_compare = functools.partial(ppo_cases._compare, k_grad=K_GRAD)
 
 SHAPES = {
     "production_ragged": (261, 2, 12, 37),
@@ -93,125 +90,6 @@ VARIANTS = {
     "value_coef": dict(value_loss_coef=0.5),
     "plain_value_coef": dict(use_clipped_value_loss=False, value_loss_coef=2.0),
 }
-
-
-@contextlib.contextmanager
-def _args(**over):
-    """PPO_Args attributes set for the duration of a case."""
-    A = R.PPO_Args
-    old = {k: getattr(A, k) for k in over}
-    try:
-        for k, v in over.items():
-            setattr(A, k, v)
-        yield A
-    finally:
-        for k, v in old.items():
-            setattr(A, k, v)
-
-
-class _Case:
-    """A fresh engine on a storage whose mini-batch rows populate every branch of the loss (module docstring)."""
-
-    def __init__(self, hist, priv, na, mb, window=0, seed=0):
-        g = torch.Generator().manual_seed(1000 * seed + hist + 7 * priv + 13 * na + mb)
-        self.hist, self.priv, self.na, self.mb = hist, priv, na, mb
-        rows = self.rows = mb + max(3, mb // 7)
-        torch.manual_seed(seed + 5)
-        ac = R.ActorCritic(70, priv, hist, na)
-        with torch.no_grad():  # biases and std off their initial 0 / 1, so that each one matters
-            for n, p in ac.named_parameters():
-                if n.endswith("bias"):
-                    p.add_(0.05 * torch.randn(p.shape, generator=g))
-            ac.std.copy_(0.6 + 0.8 * torch.rand(na, generator=g))
-        self.alg = alg = R.PPO(ac, device=DEV)
-        perm = torch.randperm(rows, generator=g)
-        at = int((perm == rows - 1).nonzero())
-        if at >= mb:  # the last storage row is part of the mini-batch
-            perm[[mb // 2, at]] = perm[[at, mb // 2]]
-        self.idx = idx = perm[:mb].to(DEV)
-        assert int(idx.max()) == rows - 1 and rows > mb
-        # ---- storage: random rows, then the mini-batch's rows from the f64 forward
-        wide = torch.randn(1, rows, hist + (350 if window else 0), generator=g).to(DEV)
-        st = types.SimpleNamespace(num_envs=rows, num_transitions_per_env=1)
-        st.observation_histories = wide[:, :, window:window + hist] if window else wide
-        st.privileged_observations = (0.5 * torch.randn(1, rows, priv, generator=g)).to(DEV)
-        for k, w in (("actions", na), ("mu", na), ("values", 1), ("advantages", 1), ("returns", 1),
-                     ("actions_log_prob", 1)):
-            setattr(st, k, torch.randn(1, rows, w, generator=g).to(DEV))
-        st.sigma = (0.5 + torch.rand(1, rows, na, generator=g)).to(DEV)
-        ac64 = ppo_ref.double_copy(alg.actor_critic)
-        m = torch.arange(mb)
-        with torch.no_grad():
-            h = st.observation_histories[0, idx].double()
-            pv = st.privileged_observations[0, idx].double()
-            mu64 = ac64.actor_body(torch.cat((h, ac64.adaptation_module(h)), -1))
-            v64 = ac64.critic_body(torch.cat((h, pv), -1))
-            std = ac64.std.detach()
-            z = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64).to(DEV)  # noqa: E731
-            actions = (mu64 + std * z(mb, na)).float()
-            logp64 = torch.distributions.Normal(mu64, std).log_prob(actions.double()).sum(-1, keepdim=True)
-            delta = torch.tensor(DELTAS, dtype=torch.float64)[m % 5].to(DEV)[:, None]
-            sign = torch.where(m % 2 == 0, 1.0, -1.0).double().to(DEV)[:, None]
-            big = torch.where((m % 4 == 3) | (m == mb - 1), 10.0, 1.0).double().to(DEV)[:, None]
-            adv = sign * big * (0.5 + z(mb, 1).abs())
-            voff = torch.tensor(VOFFS, dtype=torch.float64)[m % 4].to(DEV)[:, None]
-            flip = torch.where(torch.rand(mb, na, generator=g) < 0.5, -1.0, 1.0).double().to(DEV)
-            sig_old = std * (1.0 + 0.01 * torch.where(m % 2 == 0, 1.0, -1.0).double().to(DEV)[:, None])
-            sig_old = sig_old.expand(mb, na)
-            mu_old = mu64 + flip * std * math.sqrt(2.0 * KL0 / na)
-            for k, v in (("actions", actions), ("actions_log_prob", logp64 + delta), ("advantages", adv),
-                         ("values", v64 + voff), ("returns", v64 + z(mb, 1)), ("mu", mu_old), ("sigma", sig_old)):
-                getattr(st, k)[0, idx] = v.float()
-        self.storage = alg.storage = st
-        self.eng = PE.PPOEngine(alg)
-        self.rows32 = ppo_ref.rows_of(st)
-        self.rows64 = ppo_ref.rows_of(st, torch.float64)
-
-    def start(self, world=1):
-        """_bind, _write_hyper, pack, idx: ready for grad(0).  Returns the hyper-parameter dict of the restatement."""
-        e = self.eng
-        e._bind(self.storage, self.mb)
-        e._write_hyper(R.PPO_Args, world)
-        e.pack()
-        e.idx.copy_(self.idx)
-        return ppo_ref.hyper_from_args(R.PPO_Args)
-
-    def ac64(self):
-        """The engine's current parameters as a float64 module."""
-        torch.cuda.synchronize()
-        return ppo_ref.double_copy(self.alg.actor_critic)
-
-    def split(self, flat_vec, adaptation_only=False):
-        return list(self.eng._views(flat_vec, adaptation_only).values())
-
-
-def _errs(g, g64):
-    """(max |g - g64| / max |g64|, relative L2 error) of one tensor."""
-    g, g64 = g.double().reshape(-1), g64.double().reshape(-1)
-    d = g - g64
-    return (float(d.abs().max() / g64.abs().max()), float(d.norm() / g64.norm()))
-
-
-def _compare(tag, names, eng, yard, ref, worst, row_terms):
-    """Engine within K_GRAD x the yardstick (both against f64), tensor by tensor, on both metrics.  `row_terms`:
-    the f64 per-row terms t[r, c] of the tensors that are plain sums over the rows; their floor is 2^-24 x the
-    condition number of the sum (module docstring)."""
-    bad = []
-    for n, a, y, r in zip(names, eng, yard, ref):
-        assert float(r.double().abs().max()) > 0.0, (tag, n)
-        floors = [FLOOR, FLOOR]
-        if n in row_terms:
-            mag = row_terms[n].double().abs().sum(0).reshape(-1)  # sum_r |t[r, c]| per output element
-            r1 = r.double().reshape(-1)
-            floors = [FLOOR * max(1.0, float(mag.max() / r1.abs().max())),
-                      FLOOR * max(1.0, float(mag.norm() / r1.norm()))]
-        for metric, ea, ey, fl in zip(("max", "l2"), _errs(a, r), _errs(y, r), floors):
-            ratio = max(ea, fl) / max(ey, fl)
-            if ratio > worst[0]:
-                worst[:] = [ratio, f"{tag}:{n}:{metric} engine {ea:.2e} yardstick {ey:.2e}"]
-            if not ratio <= K_GRAD:
-                bad.append((tag, n, metric, ea, ey))
-    return bad
 
 
 def _check_branches(r64, clip, clipped_value):

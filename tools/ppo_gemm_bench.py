@@ -1,4 +1,4 @@
-"""Time the PPO engine's two GEMM kernels (csrc/ppo_update.hip xw_kernel, wgrad_kernel) at the update's shapes,
+"""Time the PPO engine's two GEMM kernels (csrc/ppo_xw.h xw_kernel, csrc/ppo_wgrad.h wgrad_kernel) at the update's shapes,
 for one or more builds of the library: python tools/ppo_gemm_bench.py [lib.so ...]
 
 Per shape: (time of 1 + R launches - time of 1 launch) / R with HIP events, and the f16-MFMA rate of the 3xF16
