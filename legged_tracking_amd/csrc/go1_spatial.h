@@ -18,8 +18,9 @@ struct SI {
 // integrator is compared with the f64 oracle within a tolerance, never bitwise.
 __device__ __forceinline__ float frcp(float x) { return __builtin_amdgcn_rcpf(x); }
 // hardware v_sin_f32 / v_cos_f32 on the angle in revolutions reduced to [0, 1) by v_fract_f32:
-// 5 issue slots instead of the portable polynomial's ~25 (integrator only; absolute error
-// ~1e-6, the step is compared with the f64 oracle within a tolerance)
+// 5 issue slots instead of the portable polynomial's ~25 (integrator only; absolute error 7.3e-7 over the joint
+// range |x| <= 8, growing by 2^-22 |x| -- the rounding of x / 2 pi, which fract cannot recover: measured in
+// tests/test_gpu_device_math.py; the step is compared with the f64 oracle within a tolerance)
 __device__ __forceinline__ void hw_sincosf(float x, float* s, float* c) {
   const float r = __builtin_amdgcn_fractf(x * 0.159154943091895336f);
   *s = __builtin_amdgcn_sinf(r);

@@ -1960,3 +1960,42 @@ void go1o_point_inertia(const double* Rb9, const double* lp9, const double* Mp9,
   point_inertia(Rb, lp, Mp, &I);
   for (int i = 0; i < 36; ++i) out36[i] = I.m[i / 6][i % 6];
 }
+
+/* batch test exports (tests/test_portable_math.py, tests/test_gpu_device_*.py): the portable f32 math and the torch-
+ * order helpers on arrays, for comparison with float64 and, bit for bit, with the HIP device functions; the segment
+ * searches on arrays (inputs and results in double, the search in `real`: the f32 build gives the f32 restatement) */
+void go1o_pm_batch(int fn, const float* x, float* o0, float* o1, int n) {
+  for (int i = 0; i < n; ++i) {
+    if (fn == 0) pm_sincosf(x[i], &o0[i], &o1[i]);
+    else if (fn == 1) o0[i] = pm_asinf(x[i]);
+    else if (fn == 2) o0[i] = pm_atanf(x[i]);
+    else o0[i] = wrap_to_pi_f(x[i]);
+  }
+}
+void go1o_pm2_batch(int fn, const float* a, const float* b, float* o, int n) {
+  for (int i = 0; i < n; ++i) o[i] = fn == 0 ? pm_atan2f(a[i], b[i]) : remainder_f(a[i], b[i]);
+}
+void go1o_quat_batch(int fn, const float* q, const float* v, float* o, int n) {
+  for (int i = 0; i < n; ++i) {
+    if (fn == 0) quat_rotate_inverse_f(q + 4 * i, v + 3 * i, o + 3 * i);
+    else quat_to_rpy_f(q + 4 * i, o + 3 * i);
+  }
+}
+void go1o_seg_closest_batch(const double* P0, const double* P1, const double* Q0, const double* Q1, double* st, int n) {
+  for (int i = 0; i < n; ++i) go1o_seg_closest(P0 + 3 * i, P1 + 3 * i, Q0 + 3 * i, Q1 + 3 * i, st + 2 * i);
+}
+void go1o_seg_deepest_batch(const float* tile, int nx, int ny, double hs, const double* A, const double* B,
+                            const double* r, double* t, int n) {
+  for (int i = 0; i < n; ++i) t[i] = go1o_seg_deepest(tile, nx, ny, hs, A + 3 * i, B + 3 * i, r[i]);
+}
+/* R: (n, 9) row-major base-to-world rotations, pos: (n, 3), th: the box's half extents */
+void go1o_seg_box_t_batch(const double* P0, const double* P1, const double* R9, const double* pos, const double* th3,
+                          double* t, int n) {
+  real th[3] = {(real)th3[0], (real)th3[1], (real)th3[2]};
+  for (int i = 0; i < n; ++i) {
+    real p0[3], p1[3], ps[3], R[3][3];
+    for (int k = 0; k < 3; ++k) { p0[k] = (real)P0[3 * i + k]; p1[k] = (real)P1[3 * i + k]; ps[k] = (real)pos[3 * i + k]; }
+    for (int k = 0; k < 9; ++k) R[k / 3][k % 3] = (real)R9[9 * i + k];
+    t[i] = (double)seg_box_t(p0, p1, R, ps, th);
+  }
+}

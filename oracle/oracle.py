@@ -43,6 +43,9 @@ def lib(precision="f64"):
             C.c_double, C.c_void_p]
         _lib.go1o_energy.argtypes = [C.POINTER(abi.Go1Config)] + [C.c_void_p] * 7 + [C.c_double]
         _lib.go1o_energy.restype = C.c_double
+        _lib.go1o_pm_batch.argtypes = [C.c_int] + [C.c_void_p] * 3 + [C.c_int]
+        _lib.go1o_pm2_batch.argtypes = [C.c_int] + [C.c_void_p] * 3 + [C.c_int]
+        _lib.go1o_quat_batch.argtypes = [C.c_int] + [C.c_void_p] * 3 + [C.c_int]
     return _lib
 
 
@@ -93,6 +96,105 @@ def seg_closest(P0, P1, Q0, Q1):
     f.argtypes = [C.c_void_p] * 5
     f(*(x.ctypes.data for x in args), st.ctypes.data)
     return float(st[0]), float(st[1])
+
+
+def _f(x, shape=None):
+    a = np.ascontiguousarray(x, np.float32)
+    return a if shape is None else a.reshape(shape)
+
+
+def pm_sincos(x):
+    """(sin, cos) of the f32 array x by the oracle's portable_math.h pm_sincosf."""
+    x = _f(x).ravel()
+    s, c = np.empty_like(x), np.empty_like(x)
+    lib().go1o_pm_batch(0, abi.ptr(x), abi.ptr(s), abi.ptr(c), C.c_int(x.size))
+    return s, c
+
+
+def _pm1(fn, x):
+    x = _f(x).ravel()
+    o = np.empty_like(x)
+    lib().go1o_pm_batch(fn, abi.ptr(x), abi.ptr(o), None, C.c_int(x.size))
+    return o
+
+
+def pm_asin(x):
+    return _pm1(1, x)
+
+
+def pm_atan(x):
+    return _pm1(2, x)
+
+
+def wrap_to_pi(x):
+    return _pm1(3, x)
+
+
+def _pm2(fn, a, b):
+    a, b = _f(a).ravel(), _f(b).ravel()
+    assert a.size == b.size
+    o = np.empty_like(a)
+    lib().go1o_pm2_batch(fn, abi.ptr(a), abi.ptr(b), abi.ptr(o), C.c_int(a.size))
+    return o
+
+
+def pm_atan2(y, x):
+    return _pm2(0, y, x)
+
+
+def remainder(a, b):
+    """The oracle's restatement of torch.remainder on f32 arrays (b: an array of a's size)."""
+    return _pm2(1, a, b)
+
+
+def quat_rotate_inverse(q, v):
+    q, v = _f(q, (-1, 4)), _f(v, (-1, 3))
+    o = np.empty_like(v)
+    lib().go1o_quat_batch(0, abi.ptr(q), abi.ptr(v), abi.ptr(o), C.c_int(len(q)))
+    return o
+
+
+def quat_to_rpy(q):
+    q = _f(q, (-1, 4))
+    o = np.empty((len(q), 3), np.float32)
+    lib().go1o_quat_batch(1, abi.ptr(q), None, abi.ptr(o), C.c_int(len(q)))
+    return o
+
+
+def seg_closest_batch(P0, P1, Q0, Q1, precision="f64"):
+    """(n, 2) parameters (s, t) of the closest points of n segment pairs; precision="f32": the f32 oracle build."""
+    args = [np.ascontiguousarray(x, np.float64).reshape(-1, 3) for x in (P0, P1, Q0, Q1)]
+    st = np.empty((len(args[0]), 2))
+    f = lib(precision).go1o_seg_closest_batch
+    f.argtypes = [C.c_void_p] * 5 + [C.c_int]
+    f(*(x.ctypes.data for x in args), st.ctypes.data, len(st))
+    return st
+
+
+def seg_deepest_batch(tile, hs, A, B, r):
+    """t of the deepest points of n segments against one (2, nx, ny) tile at the origin (f64 oracle)."""
+    tl = np.ascontiguousarray(tile, np.float32)
+    a, b = (np.ascontiguousarray(x, np.float64).reshape(-1, 3) for x in (A, B))
+    rr = np.ascontiguousarray(np.broadcast_to(np.asarray(r, np.float64), len(a)))
+    t = np.empty(len(a))
+    f = lib().go1o_seg_deepest_batch
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 4 + [C.c_int]
+    f(tl.ctypes.data, int(tl.shape[1]), int(tl.shape[2]), float(hs), a.ctypes.data, b.ctypes.data, rr.ctypes.data,
+      t.ctypes.data, len(a))
+    return t
+
+
+def seg_box_t(P0, P1, R, pos, th, precision="f64"):
+    """t of the points of n segments nearest the box of half extents th at pose (R (n, 3, 3) base-to-world, pos):
+    go1_oracle.c seg_box_t; precision="f32": the f32 oracle build."""
+    p0, p1, ps = (np.ascontiguousarray(x, np.float64).reshape(-1, 3) for x in (P0, P1, pos))
+    rr = np.ascontiguousarray(R, np.float64).reshape(-1, 9)
+    h = _d(th, 3)
+    t = np.empty(len(p0))
+    f = lib(precision).go1o_seg_box_t_batch
+    f.argtypes = [C.c_void_p] * 6 + [C.c_int]
+    f(p0.ctypes.data, p1.ctypes.data, rr.ctypes.data, ps.ctypes.data, h.ctypes.data, t.ctypes.data, len(t))
+    return t
 
 
 def energy(cfg, body, g, payload):

@@ -72,6 +72,27 @@ def test_every_include_is_watched_by_needs_build(name):
                 assert inc in watched, f"{name} is not rebuilt when {inc} changes (included by {f})"
 
 
+def test_devcheck_library_is_built_as_the_step_kernels_are_and_loads():
+    """The test-only device-function library (csrc/go1_devcheck.hip, tests/devcheck.py) is a row of build.LIBS with
+    the step libraries' flags, made of go1_device.h and its parts, and loads without a GPU with every launcher the
+    binding names; no product source names it."""
+    from tests import devcheck as D
+    srcs, flags = B.LIBS[D.NAME]
+    assert srcs == ["go1_devcheck.hip"] and flags == B.STEP_FLAGS
+    assert os.path.join(CSRC, "go1_device.h") in B.lib_files(D.NAME)
+    step_parts = {f for f in SCANNED if f.endswith(".h") and os.path.basename(f) != "go1_step_shared.h"}
+    assert step_parts <= set(B.lib_files(D.NAME))
+    lib = D.lib()
+    for fn in ("go1dc_pm1", "go1dc_pm2", "go1dc_softsign2", "go1dc_quat", "go1dc_solve6", "go1dc_lanes",
+               "go1dc_seg_closest", "go1dc_seg_box_t", "go1dc_terrain"):
+        assert getattr(lib, fn) is not None
+    pkg = os.path.join(ROOT, "legged_tracking_amd")
+    for dirpath, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith((".py", ".h", ".hip")) and f not in ("build.py", "go1_devcheck.hip"):
+                assert "devcheck" not in open(os.path.join(dirpath, f), errors="ignore").read(), f
+
+
 @pytest.mark.skipif(not shutil.which(HIPCC) and not os.path.exists(HIPCC), reason="hipcc not available")
 def test_diagnostic_builds_compile():
     variants = [([], SRC)] + [([f"-D{s}"], SRC) for s in _switches()] + [(["-DGO1_VEL_STAMPS"], VEL_SRC)]
