@@ -24,6 +24,14 @@
  * builds both optimizers over every parameter and the adaptation loss back-propagates through the encoder
  * (:170-190), so the adaptation optimizer's slice is encoder + adaptation module.
  *
+ * The same module with the CNN encoder (use_cnn, actor_critic.py:36-45; enc_mode = GO1_PPO_ENC_CNN) on the
+ * reference's (2, 61, 31) map:  emb = W feat + b (no activation),  feat = the 3360 values of
+ *   map -> conv 3x3 pad 1 (2 -> 16) -> ReLU -> pool 2 -> conv 3x3 pad 1 (16 -> 32) -> ReLU -> pool 2.
+ * One pass per phase as above.  The conv stack runs in one kernel per direction (csrc/ppo_conv.h): the backward
+ * computes the forward again from the map in LDS, so no activation is stored per row; pool ties go to the first
+ * maximum in torch's scan order and ReLU'(0) = 0; the filters' gradients leave as one partial per workgroup and are
+ * summed in workgroup order.
+ *
  * Arithmetic: the GEMMs run on v_mfma_f32_16x16x32_f16 with every f32 operand split into hi + lo f16 halves
  * after an exact power-of-two scaling per tensor (3 MFMAs per product: hi*hi + hi*lo + lo*hi, f32
  * accumulation); everything else (biases, ELU, the loss, its gradient, reductions, Adam) is f32 / f64 VALU.
@@ -56,6 +64,9 @@ extern "C" {
 /* the encoder in front of the heads (go1_ppo_dims.enc_mode) */
 #define GO1_PPO_ENC_NONE 0
 #define GO1_PPO_ENC_MLP 1
+/* the CNN encoder.  The value 2 is skipped: a caller built against the MLP-only header that probes enc_mode 2 for
+   "the next encoder" is still refused, with the message it was refused with before (tests pin it) */
+#define GO1_PPO_ENC_CNN 3
 #define GO1_PPO_ENC_HIDDEN 256   /* the MLP encoder's hidden width */
 #define GO1_PPO_ENC_MAX_MAP 4096
 #define GO1_PPO_ENC_MAX_EMBED 512
@@ -69,10 +80,11 @@ typedef struct go1_ppo_dims {
   int32_t actions;  /* num_actions, 1..16 */
   int32_t mb;       /* mini-batch rows (num_envs * num_steps_per_env / num_mini_batches) */
   int64_t rows;     /* storage rows (num_steps_per_env * num_envs); every idx value < rows */
-  /* ABI 2, all zero: the plain module.  With enc_mode = GO1_PPO_ENC_MLP `hist` stays the stored history width, a
-     multiple of num_obs, and the heads' input width is 2 (num_obs - n_map) + n_embed.  Refused (GO1_PPO_E_ARG): any
-     other enc_mode, n_embed not a multiple of 128 or above 512, n_map outside 1..min(4096, num_obs), hist not a
-     multiple of num_obs. */
+  /* ABI 2, all zero: the plain module.  With enc_mode = GO1_PPO_ENC_MLP or GO1_PPO_ENC_CNN `hist` stays the stored
+     history width, a multiple of num_obs, and the heads' input width is 2 (num_obs - n_map) + n_embed.  Refused
+     (GO1_PPO_E_ARG): any other enc_mode, n_embed not a multiple of 128 or above 512, n_map outside
+     1..min(4096, num_obs), hist not a multiple of num_obs; with GO1_PPO_ENC_CNN any n_map but 3782 (the dims do not
+     carry the map's x and y: the CNN mode takes the (2, 61, 31) map and nothing else). */
   int32_t enc_mode;
   int32_t num_obs;  /* width of one observation frame: [scalars | map] */
   int32_t n_map;    /* prod(height_map_shape), the trailing columns of a frame */
@@ -99,7 +111,8 @@ typedef struct go1_ppo_bufs {
   const int64_t* idx;            /* (mb) storage rows of the mini-batch (mini_batch_generator's permutation slice) */
   /* flat f32 parameters in state_dict order (adaptation_module.{0,2,4}, actor_body.{0,2,4,6},
      critic_body.{0,2,4,6}, each weight then bias; std last): go1_ppo_param_count() floats.  With an encoder its
-     parameters lead: height_map_encoder.model.{0,2}, then the above (the module's own order has std first) */
+     parameters lead: height_map_encoder.model.{0,2} (MLP) or .{0,3,7} (CNN: conv1, conv2, linear), then the above
+     (the module's own order has std first) */
   float* params;
   float* grads;                  /* GO1_PPO_AUX + go1_ppo_param_count() floats: aux sums, then the flat gradient */
   float *exp_avg, *exp_avg_sq;   /* PPO.optimizer Adam state, flat like params */
@@ -141,6 +154,17 @@ int go1_ppo_test_linear(const float* x, int64_t rows, int32_t k, const float* w,
                         int32_t elu, float* y, void* work, int64_t work_bytes, int32_t reps, void* stream);
 int go1_ppo_test_wgrad(const float* x, const float* d, int64_t rows, int32_t k, int32_t n, float* dw, void* work,
                        int64_t work_bytes, int32_t reps, void* stream);
+/* test entry point of the CNN height-map encoder's convolution stack (csrc/ppo_conv.h; ppo_cse_cnn/actor_critic.py:
+   36-44 on the reference's (2, 61, 31) map): maps (rows, 3782) -> conv 3x3 pad 1 (2 -> 16), ReLU, pool 2, conv 3x3
+   pad 1 (16 -> 32), ReLU, pool 2 -> feat (rows, 3360), and for d_feat (rows, 3360), the gradient of a loss by the
+   features, the loss's gradients by the filters w1 (16, 2, 3, 3), w2 (32, 16, 3, 3) and the biases, summed over the
+   rows in a fixed order.  The forward is computed again for the backward; nothing is stored per row.  Pool ties go to
+   the first maximum in torch's scan order, ReLU'(0) = 0.  These are the kernels of enc_mode GO1_PPO_ENC_CNN, on
+   caller tensors.  work: 256-byte aligned, 41,216 + 19,776 * min(rows, 256) bytes; rows <= 2^24;
+   the kernel launch is repeated `reps` times (timing; same result) */
+int go1_ppo_test_conv(const float* maps, int64_t rows, const float* w1, const float* b1, const float* w2,
+                      const float* b2, const float* d_feat, float* feat, float* dw1, float* db1, float* dw2,
+                      float* db2, void* work, int64_t work_bytes, int32_t reps, void* stream);
 
 #ifdef __cplusplus
 }

@@ -133,6 +133,9 @@ struct EmbArgs {
   float* colsum;              // [tiles_m][E]
   uint32_t* dmax;
   int32_t M, E;
+  // the CNN encoder's embedding has no activation (act 0: no ELU' factor); its phase 1 has the adaptation module's
+  // term alone (nsrc 1: t_a; t_p and t_c are not read)
+  int32_t act, nsrc;
 };
 
 __global__ __launch_bounds__(256) void embgrad_kernel(EmbArgs a) {
@@ -147,14 +150,18 @@ __global__ __launch_bounds__(256) void embgrad_kernel(EmbArgs a) {
     const int m = mt * TB + rl + 8 * i;
     const bool in = m < a.M;
     const size_t o = (size_t)min(m, a.M - 1) * a.E + n;
-    const f4_t tp = *reinterpret_cast<const f4_t*>(a.tp + o);
-    const f4_t tc = *reinterpret_cast<const f4_t*>(a.tc + o);
     const f4_t ta = *reinterpret_cast<const f4_t*>(a.ta + o);
-    const f4_t e = *reinterpret_cast<const f4_t*>(a.emb + (size_t)min(m, a.M - 1) * a.lde + n);
+    f4_t tp = ta, tc = ta, e = ta;
+    if (a.nsrc == 3) {  // uniform
+      tp = *reinterpret_cast<const f4_t*>(a.tp + o);
+      tc = *reinterpret_cast<const f4_t*>(a.tc + o);
+    }
+    if (a.act) e = *reinterpret_cast<const f4_t*>(a.emb + (size_t)min(m, a.M - 1) * a.lde + n);
     f4_t v;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      v[j] = in ? ((tp[j] + tc[j]) + ta[j]) * delu_from_out(e[j]) : 0.0f;
+      const float t = a.nsrc == 3 ? (tp[j] + tc[j]) + ta[j] : ta[j];
+      v[j] = in ? (a.act ? t * delu_from_out(e[j]) : t) : 0.0f;
       mx = max(mx, absbits(v[j]));
     }
     cs += v;

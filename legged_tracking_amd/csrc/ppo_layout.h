@@ -14,12 +14,21 @@ enum MaxSlot {
   // the encoder: the gathered map, its hidden layer, d emb, d hidden.  The embedding's maximum goes to MX_LAT, the
   // slot of G's computed columns (embedding, latent): the first layers' scale max(MX_G, MX_LAT) bounds it
   MX_MAP, MX_E1, MX_DEMB, MX_DE1,
+  // the CNN encoder: the conv stack's features (the input of its linear layer) and their gradient.  MX_DFEAT is a
+  // record only (the issue's "max |d feat| in a new max slot"): no kernel scales by it, conv_kernel takes each row's
+  // own maximum of d feat in LDS, which rows of mixed magnitude need
+  MX_FEAT, MX_DFEAT,
   MX_N
 };
-// one weight image per GEMM layer: the adaptation module's, the actor's and the critic's first three, the encoder's two
+// one weight image per GEMM layer: the adaptation module's, the actor's and the critic's first three, the MLP
+// encoder's two
 enum WSlot { W_A0 = 0, W_A2, W_P0, W_P2, W_P4, W_C0, W_C2, W_C4, W_E0, W_E2, W_N };
 constexpr int W_PLAIN = W_E0;  // the slots of the plain module
+// the CNN encoder has one GEMM layer, Linear(3360, E), in the slot W_E0 (the MLP's W_E2 is then unused); its two
+// convolutions are conv_kernel's (ppo_conv.h), with their scale exponents in the two wexp records after the layers'
+constexpr int W_CNN = W_E0, WEXP_CONV = W_N;
 constexpr int ENC_H = GO1_PPO_ENC_HIDDEN;
+constexpr int CV_DPAD = (CV_NFEAT + TB - 1) / TB * TB;  // d feat's row: 3360 padded to the xw tile, 3456
 // parameter indices: a0 a2 a4 | p0 p2 p4 p6 | c0 c2 c4 c6 | the encoder's e0 e2 (first in the flat buffers)
 enum { IA0 = 0, IA2, IA4, IP0, IP2, IP4, IP6, IC0, IC2, IC4, IC6, IE0, IE2 };
 
@@ -45,6 +54,10 @@ struct Layer {
                  // transposed image to reach that one's delta.  -1: the backward ends here (or takes another kernel)
   bool adapt;    // in the adaptation optimizer's slice: phase 1 runs it again
   bool first;    // reads the gathered rows G: with an encoder its image's columns are permuted (pack_kernel)
+  bool lin;      // no activation: out = in W^T + b (the CNN encoder's linear layer)
+  int kt_own;    // columns of a transposed image the layer needs although no table row is below it (0: none).  Columns
+                 // past k are padding that the pack never writes: they are zero because the caller zeroes the
+                 // workspace once before first use (go1_ppo.h), as the zero bias `zbias` is
   int gap;       // first layers: G columns at H that the parameter does not have (the critic skips the latent)
   // derived by make_layout: the transposed image's columns (0: none) and the workspace offsets
   int kt;
@@ -65,6 +78,9 @@ struct Lay {
   // workspace byte offsets: the records, then the buffers that kernels other than the GEMMs name
   size_t maxes, wmax, wexp, scal, normp, G, Bb, a2a, p3, c3, d3p, d3c, d1p, d2a, hpart, apart, total;
   size_t mapb, demb, tp, tc, ta, csemb, zbias;  // the encoder's
+  int64_t pwc[2], pbc[2];                        // the CNN encoder's conv filters and biases (floats)
+  size_t feat, dfeat, cvimg, cvpart;             // its features, their gradient, the filters' images, the partials
+  int cvS, cvG;                                  // conv_kernel's strip and workgroups for mb rows
   Layer layer[W_N];
 };
 
@@ -79,9 +95,10 @@ bool make_layout(const go1_ppo_dims* d, Lay& L, std::string& err) {
   L.Hs = L.H = d->hist;
   L.nW = W_PLAIN;
   if (d->enc_mode != GO1_PPO_ENC_NONE) {
-    if (d->enc_mode != GO1_PPO_ENC_MLP) {
+    const bool cnn = d->enc_mode == GO1_PPO_ENC_CNN;
+    if (d->enc_mode != GO1_PPO_ENC_MLP && !cnn) {
       err = "go1_ppo: enc_mode " + std::to_string(d->enc_mode) + " is not implemented (0: no encoder, 1: the MLP "
-            "encoder; the CNN encoder's backward is not on the engine)";
+            "encoder, 3: the CNN encoder on the (2, 61, 31) map)";
       return false;
     }
     if (d->n_embed < TB || d->n_embed % TB != 0 || d->n_embed > GO1_PPO_ENC_MAX_EMBED) {
@@ -90,6 +107,11 @@ bool make_layout(const go1_ppo_dims* d, Lay& L, std::string& err) {
     }
     if (d->n_map < 1 || d->n_map > GO1_PPO_ENC_MAX_MAP || d->n_map > d->num_obs) {
       err = "go1_ppo: n_map " + std::to_string(d->n_map) + " is not implemented (1..4096 map values, at most num_obs)";
+      return false;
+    }
+    if (cnn && d->n_map != CV_NMAP) {
+      err = "go1_ppo: n_map " + std::to_string(d->n_map) + " is not implemented with the CNN encoder (3782: the (2, 61, "
+            "31) map, whose twice-pooled size is the encoder's Linear(3360, E))";
       return false;
     }
     if (d->hist % d->num_obs != 0) {
@@ -103,8 +125,9 @@ bool make_layout(const go1_ppo_dims* d, Lay& L, std::string& err) {
     L.H = 2 * L.SC + L.E;
     L.foff = d->hist - d->num_obs;
     L.ldm = cdiv(L.NM, 4) * 4;
-    L.nW = W_N;
+    L.nW = cnn ? W_CNN + 1 : W_N;
   }
+  const bool cnn = L.enc == GO1_PPO_ENC_CNN;
   L.P = d->priv;
   L.A = d->actions;
   L.M = d->mb;
@@ -120,7 +143,19 @@ bool make_layout(const go1_ppo_dims* d, Lay& L, std::string& err) {
                            (int64_t)H1 * (H + P), H2 * H1, H3 * H2, 1 * H3};
   const int64_t bsz[11] = {HA1, HA2, P, H1, H2, H3, A, H1, H2, H3, 1};
   int64_t o = 0;
-  if (L.enc) {  // the encoder leads the flat buffers: the adaptation optimizer's slice is encoder + adaptation module
+  if (cnn) {  // [conv1 w, b | conv2 w, b | linear w, b], the module's order
+    const int64_t csz[2] = {CV_C1 * CV_K1, CV_C2 * CV_K2}, cb[2] = {CV_C1, CV_C2};
+    for (int i = 0; i < 2; ++i) {
+      L.pwc[i] = o;
+      o += csz[i];
+      L.pbc[i] = o;
+      o += cb[i];
+    }
+    L.pw[IE2] = o;
+    o += (int64_t)E * CV_NFEAT;
+    L.pb[IE2] = o;
+    o += E;
+  } else if (L.enc) {  // the encoder leads the flat buffers: the adaptation optimizer's slice is encoder + adaptation module
     L.pw[IE0] = o;
     o += (int64_t)ENC_H * L.NM;
     L.pb[IE0] = o;
@@ -174,7 +209,16 @@ bool make_layout(const go1_ppo_dims* d, Lay& L, std::string& err) {
     L.tc = rows(E);
     L.ta = rows(E);
     L.csemb = sums(E);
-    L.zbias = take(GO1_PPO_ENC_MAX_EMBED * F);  // zeros (never written): the bias of the xw<LIN> products
+    // zeros (never written): the bias of the xw<LIN> products
+    L.zbias = take((size_t)(cnn ? CV_DPAD : GO1_PPO_ENC_MAX_EMBED) * F);
+  }
+  if (cnn) {
+    L.feat = rows(CV_NFEAT);
+    L.dfeat = rows(CV_DPAD);
+    L.cvimg = take((size_t)CV_IMG_N * sizeof(h8_t));
+    L.cvS = conv_strip(L.M);
+    L.cvG = conv_groups(L.M);
+    L.cvpart = take((size_t)L.cvG * CV_PART * F);
   }
   // ---- the layer table.  A layer reads the output of the layer below it (input {}: filled in from `below`), except
   // the first layers, which read the gathered rows: the actor G's [hist, latent], the critic [hist, latent, priv] with
@@ -184,32 +228,36 @@ bool make_layout(const go1_ppo_dims* d, Lay& L, std::string& err) {
   const int hs = head_stride(A), as = adapt_stride(P), HB = L.HB;
   const HeadPart hp(A);
   const AdaptPart ap(P);
-  const int lat = L.enc ? MX_LAT : -1, emb = L.enc ? W_E2 : -1;
+  const int lat = L.enc ? MX_LAT : -1, emb = cnn ? W_CNN : (L.enc ? W_E2 : -1);
   const Mat G = {L.G, ldg, MX_G};
   Layer* T = L.layer;
   //         param n   k   input max2   output                   delta                    bias sums
   //         below adapt first gap
   T[W_A0] = {IA0, HA1, H, G, lat, {rows(HA1), HA1, MX_A1A}, {rows(HA1), HA1, MX_D1A}, {sums(HA1), MT, HA1},
-             emb, true, true, 0};
+             emb, true, true, false, 0, 0};
   T[W_A2] = {IA2, HA2, HA1, {}, -1, {L.a2a, HA2, MX_A2A}, {L.d2a, HA2, MX_D2A}, {L.apart + ap.db2a * F, HB, as},
-             W_A0, true, false, 0};
+             W_A0, true, false, false, 0, 0};
   T[W_P0] = {IP0, H1, H + P, G, MX_LAT, {rows(H1), H1, MX_P1}, {L.d1p, H1, MX_D1P}, {sums(H1), MT, H1},
-             emb, false, true, 0};
+             emb, false, true, false, 0, 0};
   T[W_P2] = {IP2, H2, H1, {}, -1, {rows(H2), H2, MX_P2}, {rows(H2), H2, MX_D2P}, {sums(H2), MT, H2},
-             W_P0, false, false, 0};
+             W_P0, false, false, false, 0, 0};
   T[W_P4] = {IP4, H3, H2, {}, -1, {L.p3, H3, MX_P3}, {L.d3p, H3, MX_D3P}, {L.hpart + hp.db3p * F, HB, hs},
-             W_P2, false, false, 0};
+             W_P2, false, false, false, 0, 0};
   T[W_C0] = {IC0, H1, H + 2 * P, G, MX_LAT, {rows(H1), H1, MX_C1}, {rows(H1), H1, MX_D1C}, {sums(H1), MT, H1},
-             emb, false, true, P};
+             emb, false, true, false, 0, P};
   T[W_C2] = {IC2, H2, H1, {}, -1, {rows(H2), H2, MX_C2}, {rows(H2), H2, MX_D2C}, {sums(H2), MT, H2},
-             W_C0, false, false, 0};
+             W_C0, false, false, false, 0, 0};
   T[W_C4] = {IC4, H3, H2, {}, -1, {L.c3, H3, MX_C3}, {L.d3c, H3, MX_D3C}, {L.hpart + hp.db3c * F, HB, hs},
-             W_C2, false, false, 0};
-  if (L.enc) {
+             W_C2, false, false, false, 0, 0};
+  if (cnn) {  // emb = feat W^T + b, no activation, into G; the conv stack below it is conv_kernel's, which takes
+              // d feat = d emb W: the transposed image of all 3360 columns, padded to the tile with zero columns
+    T[W_CNN] = {IE2, E, CV_NFEAT, {L.feat, CV_NFEAT, MX_FEAT}, -1, {L.G, ldg, MX_LAT}, {L.demb, E, MX_DEMB},
+                {L.csemb, MT, E}, -1, true, false, true, CV_DPAD, 0};
+  } else if (L.enc) {
     T[W_E0] = {IE0, ENC_H, L.NM, {L.mapb, L.ldm, MX_MAP}, -1, {rows(ENC_H), ENC_H, MX_E1},
-               {rows(ENC_H), ENC_H, MX_DE1}, {sums(ENC_H), MT, ENC_H}, -1, true, false, 0};
+               {rows(ENC_H), ENC_H, MX_DE1}, {sums(ENC_H), MT, ENC_H}, -1, true, false, false, 0, 0};
     T[W_E2] = {IE2, E, ENC_H, {}, -1, {L.G, ldg, MX_LAT}, {L.demb, E, MX_DEMB}, {L.csemb, MT, E},
-               W_E0, true, false, 0};
+               W_E0, true, false, false, 0, 0};
   }
   for (int w = 0; w < L.nW; ++w)
     if (!T[w].first && T[w].below >= 0) T[w].in = T[T[w].below].out;
@@ -232,7 +280,7 @@ bool make_layout(const go1_ppo_dims* d, Lay& L, std::string& err) {
   for (int w = 0; w < L.nW; ++w) {
     Layer& y = T[w];
     const int S = y.adapt ? std::max(L.S[0], L.S[1]) : L.S[0];
-    y.kt = y.below >= 0 ? T[y.below].n : 0;
+    y.kt = y.below >= 0 ? T[y.below].n : y.kt_own;
     y.part = take((size_t)S * y.n * y.kpad() * F);
     y.img = take((size_t)cdiv(y.k, 32) * 32 * y.n * 4);
     y.imgt = y.kt ? take((size_t)cdiv(y.n, 32) * 32 * y.kt * 4) : 0;
@@ -298,6 +346,44 @@ struct Ctx {
     XwProb p = xw_prob(opnd(y.delta), y.n, at<h8_t>(y.imgt), wexp(w), y.kt, at<float>(out), y.kt, nullptr);
     p.bias = at<float>(L.zbias);
     return p;
+  }
+  // the CNN encoder: d feat = d emb W of its linear layer, [M][3456], and its maximum (a record: MaxSlot).  The last 96
+  // columns come from the image's padding (zero with the workspace, Layer::kt_own); conv_kernel reads 3360 of a row
+  XwProb bwd_feat() const {
+    const Layer& y = L.layer[W_CNN];
+    XwProb p = xw_prob(opnd(y.delta), y.n, at<h8_t>(y.imgt), wexp(W_CNN), y.kt, at<float>(L.dfeat), y.kt, mx(MX_DFEAT));
+    p.bias = at<float>(L.zbias);
+    return p;
+  }
+  // its conv stack on the gathered maps: the features (and their maximum) alone, or the filters' gradient partials too
+  ConvPack conv_pack() const {
+    return {b->params + L.pwc[0], b->params + L.pwc[1], at<h8_t>(L.cvimg), wexp(WEXP_CONV)};
+  }
+  ConvArgs conv(bool backward) const {
+    ConvArgs a{};
+    a.map = at<float>(L.mapb);
+    a.ldm = L.ldm;
+    a.dfeat = backward ? at<float>(L.dfeat) : nullptr;
+    a.ldd = CV_DPAD;
+    a.feat = backward ? nullptr : at<float>(L.feat);
+    a.ldf = CV_NFEAT;
+    a.featmax = backward ? nullptr : mx(MX_FEAT);
+    a.img = at<h8_t>(L.cvimg);
+    a.wexp = wexp(WEXP_CONV);
+    a.b1 = b->params + L.pbc[0];
+    a.b2 = b->params + L.pbc[1];
+    a.part = at<float>(L.cvpart);
+    a.rows = L.M;
+    a.strip = L.cvS;
+    return a;
+  }
+  void conv_segs(SegBuilder& SB) const {
+    const float* pt = at<float>(L.cvpart);
+    float* g = b->grads + NAUX;
+    SB.add(g + L.pwc[0], pt + CV_OFF_DW1, 1, CV_C1 * CV_K1, 0, L.cvG, CV_PART);
+    SB.add(g + L.pbc[0], pt + CV_OFF_DB1, 1, CV_C1, 0, L.cvG, CV_PART);
+    SB.add(g + L.pwc[1], pt, 1, CV_C2 * CV_K2, 0, L.cvG, CV_PART);
+    SB.add(g + L.pbc[1], pt + CV_OFF_DB2, 1, CV_C2, 0, L.cvG, CV_PART);
   }
   // weight gradient: partials of delta^T in
   WgProb wg(int w) const {

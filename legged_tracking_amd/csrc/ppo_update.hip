@@ -32,6 +32,15 @@
 //            (W_A0[:, emb]^T delta1a) * ELU'(emb), xw<D> delta e1, wgrad of four layers; Adam and the re-pack
 //            cover encoder + adaptation module (the adaptation optimizer's slice, with its own moments).
 //
+// With the CNN encoder (enc_mode = GO1_PPO_ENC_CNN, the (2, 61, 31) map; ppo_conv.h) the encoder's part of the chain is
+//   phase 0  conv<fwd> map -> feat (3360) and max feat, xw<LIN> feat -> emb into G (no activation); the heads; the
+//            three xw<LIN> products and embgrad without the ELU' factor (d emb, its column sums = the linear layer's
+//            bias gradient), xw<LIN> d feat = d emb W over the transposed image padded to 3456 columns (max |d feat|),
+//            conv<bwd> (the forward again in LDS, then the filters' gradient partials); the linear layer's weight
+//            gradient joins the grouped wgrad launch, the conv partials the reduce (four segments)
+//   phase 1  conv<fwd>, xw<LIN> again; d emb = W_A0[:, emb]^T delta1a (xw<LIN>, embgrad with that one source),
+//            d feat, conv<bwd>; Adam and the re-pack (conv_pack + pack) cover [conv1 | conv2 | linear | adaptation]
+//
 // GEMMs ("xw": activations x weights^T, "wgrad": delta^T x activations) run on v_mfma_f32_16x16x32_f16 with
 // f32 accuracy from the 3xF16 split (hi = f16(x), lo = f16(x - hi), products hi*hi + hi*lo + lo*hi, f32
 // accumulation; the dropped lo*lo term is ~2^-22 of a product).  Every operand tensor is first scaled by an
@@ -47,6 +56,7 @@
 //   ppo_xw.h      xw_kernel, its problem builder and launch          ppo_wgrad.h   wgrad_kernel, likewise
 //   ppo_gather.h  gather_kernel, embgrad_kernel                      ppo_heads.h   head_kernel, adapt_kernel
 //   ppo_step.h    reduce, norm, finalize, adam, wmax / pack, absmax, zero, and the tables they take
+//   ppo_conv.h    conv_pack_kernel, conv_kernel: the CNN encoder's convolution stack, forward and backward
 //   ppo_layout.h  host only: slots, the workspace layout, the table of the GEMM layers and the problems of a layer
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -78,6 +88,7 @@ int fail(int code, const std::string& m) {
 #include "ppo_gather.h"
 #include "ppo_heads.h"
 #include "ppo_step.h"
+#include "ppo_conv.h"
 #include "ppo_layout.h"
 
 namespace {
@@ -106,12 +117,16 @@ int pack_weights(const Ctx& C, bool adaptation_only, bool zero_max) {
     hipLaunchKernelGGL(zero_u32_kernel, dim3(1), dim3(64), 0, C.s, C.wmax(0), L.nW);
     PPO_TRY(hipGetLastError());
   }
+  if (L.enc == GO1_PPO_ENC_CNN) {  // the conv filters' images: the encoder is in both slices
+    hipLaunchKernelGGL(conv_pack_kernel, dim3(1), dim3(256), 0, C.s, C.conv_pack());
+    PPO_TRY(hipGetLastError());
+  }
   return launch_pack(C.s, PB);
 }
 
 int forward(const Ctx& C, int w, int w2 = -1) {
   const XwProb p = C.fwd(w), p2 = w2 >= 0 ? C.fwd(w2) : XwProb{};
-  return launch_xw(C.s, C.L.M, EPI_ELU, p, w2 >= 0 ? &p2 : nullptr);
+  return launch_xw(C.s, C.L.M, C.L.layer[w].lin ? EPI_LIN : EPI_ELU, p, w2 >= 0 ? &p2 : nullptr);
 }
 
 int backward(const Ctx& C, int w, int w2 = -1) {
@@ -133,7 +148,10 @@ int weight_grads(const Ctx& C, int phase) {
 // the gradient segments of the adaptation optimizer's slice: [encoder], adaptation module
 void adapt_slice_segments(const Ctx& C, SegBuilder& SB, int phase) {
   const Lay& L = C.L;
-  if (L.enc) {
+  if (L.enc == GO1_PPO_ENC_CNN) {
+    C.conv_segs(SB);
+    C.segs(SB, W_CNN, phase);
+  } else if (L.enc) {
     C.segs(SB, W_E0, phase);
     C.segs(SB, W_E2, phase);
   }
@@ -242,7 +260,22 @@ EmbArgs emb_args(const Ctx& C) {
   ea.dmax = C.mx(MX_DEMB);
   ea.M = L.M;
   ea.E = L.E;
+  ea.act = L.enc != GO1_PPO_ENC_CNN;
+  ea.nsrc = 3;
   return ea;
+}
+
+// the encoder's forward into G's leading columns: the MLP's two layers, or the CNN's conv stack and linear layer
+int encoder_forward(const Ctx& C) {
+  int rc;
+  if (C.L.enc == GO1_PPO_ENC_CNN) return (rc = launch_conv(C.s, C.conv(false))) ? rc : forward(C, W_CNN);
+  return (rc = forward(C, W_E0)) ? rc : forward(C, W_E2);
+}
+
+// the CNN encoder below d emb: d feat = d emb W (its maximum with it), then the conv stack's backward
+int conv_backward(const Ctx& C) {
+  int rc = launch_xw(C.s, C.L.M, EPI_LIN, C.bwd_feat());
+  return rc ? rc : launch_conv(C.s, C.conv(true));
 }
 
 // ------------------------------------------------------------------ the phases (the launch chain of the header)
@@ -264,7 +297,8 @@ int grad_phase0(const Ctx& C) {
   }
   // ---- forward: the encoder on the last frame's map (ppo_cse_cnn: process_obs_history), once for the three heads:
   // e1 = ELU(W0 map + b0), emb = ELU(W1 e1 + b1) into G's leading E columns (its maximum into MX_LAT)
-  if (L.enc && ((rc = forward(C, W_E0)) || (rc = forward(C, W_E2)))) return rc;
+  // (the CNN: conv_kernel's features, then emb = W feat + b, no activation)
+  if (L.enc && (rc = encoder_forward(C))) return rc;
   // ---- forward: adaptation module (ppo.py:110 ac.act -> update_distribution -> adaptation_module)
   if ((rc = forward(C, W_A0)) || (rc = forward(C, W_A2))) return rc;
   const AdaptArgs AD = adapt_args(C);
@@ -291,7 +325,7 @@ int grad_phase0(const Ctx& C) {
     if ((rc = launch_xw(C.s, L.M, EPI_LIN, C.bwd_lin(W_A0, L.ta)))) return rc;
     hipLaunchKernelGGL(embgrad_kernel, dim3(L.MT, L.E / TB), dim3(256), 0, C.s, emb_args(C));
     PPO_TRY(hipGetLastError());
-    if ((rc = backward(C, W_E2))) return rc;
+    if ((rc = L.enc == GO1_PPO_ENC_CNN ? conv_backward(C) : backward(C, W_E2))) return rc;
   }
   if ((rc = weight_grads(C, 0))) return rc;
   // ---- partials -> flat gradient (+ aux: surrogate, value, KL sums)
@@ -320,13 +354,24 @@ int grad_phase1(const Ctx& C) {
   int rc;
   // the gathered rows G are this mini-batch's (phase 0); the maxima phase 1 recomputes were cleared by step 0.
   // The encoder's weights moved in step 0: the embedding columns of G are computed again
-  if (L.enc && ((rc = forward(C, W_E0)) || (rc = forward(C, W_E2)))) return rc;
+  if (L.enc && (rc = encoder_forward(C))) return rc;
   if ((rc = forward(C, W_A0)) || (rc = forward(C, W_A2))) return rc;
   hipLaunchKernelGGL(adapt_kernel<1>, dim3(L.HB), dim3(256), 0, C.s, adapt_args(C));
   PPO_TRY(hipGetLastError());
   if ((rc = backward(C, W_A2))) return rc;
   // d emb = (W_A0[:, emb]^T delta1a) * ELU'(emb): the adaptation module is the only path here; then delta e1
-  if (L.enc && ((rc = backward(C, W_A0)) || (rc = backward(C, W_E2)))) return rc;
+  if (L.enc == GO1_PPO_ENC_CNN) {
+    // the CNN's embedding has no activation: d emb = W_A0[:, emb]^T delta1a as it is (embgrad: its column sums and
+    // maximum), then the conv stack
+    if ((rc = launch_xw(C.s, L.M, EPI_LIN, C.bwd_lin(W_A0, L.ta)))) return rc;
+    EmbArgs ea = emb_args(C);
+    ea.nsrc = 1;
+    hipLaunchKernelGGL(embgrad_kernel, dim3(L.MT, L.E / TB), dim3(256), 0, C.s, ea);
+    PPO_TRY(hipGetLastError());
+    if ((rc = conv_backward(C))) return rc;
+  } else if (L.enc && ((rc = backward(C, W_A0)) || (rc = backward(C, W_E2)))) {
+    return rc;
+  }
   if ((rc = weight_grads(C, 1))) return rc;
   SegBuilder SB;
   const float* ap = C.at<float>(L.apart);
@@ -367,6 +412,7 @@ int step_phase(const Ctx& C, int phase) {
     if (y.adapt) act[y.out.mx] = act[y.delta.mx] = true;
     wts[w] = phase == 0 || y.adapt;
   }
+  if (L.enc == GO1_PPO_ENC_CNN) act[MX_FEAT] = act[MX_DFEAT] = true;  // phase 1 runs the conv stack again
   if (phase == 1) std::fill(act, act + MX_N, true);
   int nr = 0;
   auto runs = [&](uint32_t* base, const bool* on, int count) {  // the set slots as runs zero[i][0 .. nz[i])
@@ -510,6 +556,50 @@ int go1_ppo_test_wgrad(const float* x, const float* d, int64_t rows, int32_t k, 
   if (rc) return rc;
   SegBuilder SB;
   SB.add(dw, part, n, k, kpad, S, p.pstride);
+  return launch_reduce(s, SB);
+}
+
+// The CNN height-map encoder's convolution stack on `rows` maps (rows, 3782): feat (rows, 3360) and, for the loss
+// gradient d_feat (rows, 3360) of the features, the filters' and biases' gradients summed over the rows
+int go1_ppo_test_conv(const float* maps, int64_t rows, const float* w1, const float* b1, const float* w2,
+                      const float* b2, const float* d_feat, float* feat, float* dw1, float* db1, float* dw2,
+                      float* db2, void* work, int64_t work_bytes, int32_t reps, void* stream) {
+  if (!maps || !w1 || !b1 || !w2 || !b2 || !d_feat || !feat || !dw1 || !db1 || !dw2 || !db2 || !work || rows < 1 ||
+      rows > (1 << 24) || (((uintptr_t)work) & 255) != 0)
+    return fail(GO1_PPO_E_ARG, "go1_ppo_test_conv: bad argument (work 256-byte aligned, 1 .. 2^24 rows)");
+  const int nwg = conv_groups((int)rows);
+  const size_t imgs = 256, parts = imgs + (size_t)CV_IMG_N * sizeof(h8_t);
+  const size_t need = parts + (size_t)nwg * CV_PART * sizeof(float);
+  if ((size_t)work_bytes < need)
+    return fail(GO1_PPO_E_ARG, "go1_ppo_test_conv: work too small (" + std::to_string(need) + " bytes)");
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)work;
+  ConvPack cp{w1, w2, (h8_t*)(ws + imgs), (int32_t*)ws};
+  hipLaunchKernelGGL(conv_pack_kernel, dim3(1), dim3(256), 0, s, cp);
+  PPO_TRY(hipGetLastError());
+  ConvArgs a{};
+  a.map = maps;
+  a.ldm = CV_NMAP;
+  a.dfeat = d_feat;
+  a.ldd = CV_NFEAT;
+  a.feat = feat;
+  a.ldf = CV_NFEAT;
+  a.featmax = nullptr;
+  a.img = cp.img;
+  a.wexp = cp.wexp;
+  a.b1 = b1;
+  a.b2 = b2;
+  a.part = (float*)(ws + parts);
+  a.rows = (int32_t)rows;
+  a.strip = conv_strip((int)rows);
+  int rc = GO1_PPO_OK;
+  for (int i = 0; !rc && i < (reps > 1 ? reps : 1); ++i) rc = launch_conv(s, a);
+  if (rc) return rc;
+  SegBuilder SB;
+  SB.add(dw2, a.part, 1, CV_C2 * CV_K2, 0, nwg, CV_PART);
+  SB.add(db2, a.part + CV_OFF_DB2, 1, CV_C2, 0, nwg, CV_PART);
+  SB.add(dw1, a.part + CV_OFF_DW1, 1, CV_C1 * CV_K1, 0, nwg, CV_PART);
+  SB.add(db1, a.part + CV_OFF_DB1, 1, CV_C1, 0, nwg, CV_PART);
   return launch_reduce(s, SB);
 }
 

@@ -14,6 +14,8 @@ GO1_ENCODER_LAYERS = 3
 GO1_ENC_MLP, GO1_ENC_CNN = 0, 1
 GO1_ENC_MAX_EMBED = 512
 GO1_PPO_ENC_NONE, GO1_PPO_ENC_MLP = 0, 1  # go1_ppo_dims.enc_mode
+GO1_PPO_ENC_CNN = 3  # 2 stays refused (go1_ppo.h)
+CNN_MAP_SHAPE, CNN_FEATURES = (2, 61, 31), 3360  # the one map the engine's CNN mode takes, its twice-pooled size
 GO1_PPO_ENC_HIDDEN = 256
 GO1_PPO_ENC_MAX_MAP = 4096
 
@@ -87,6 +89,8 @@ PPO_ARGTYPES = {
     "go1_ppo_step": [_PP(PPODims), _PP(PPOBufs), I32, P],
     "go1_ppo_test_linear": [P, I64, I32, P, P, I32, I32, P, P, I64, I32, P],
     "go1_ppo_test_wgrad": [P, P, I64, I32, I32, P, P, I64, I32, P],
+    # maps, rows, w1, b1, w2, b2, d_feat | feat, dw1, db1, dw2, db2 | work, work_bytes, reps, stream
+    "go1_ppo_test_conv": [P, I64] + [P] * 11 + [I64, I32, P],
 }
 
 # ----------------------------------------------------------------------------- the policy architecture
@@ -98,6 +102,9 @@ assert len(POLICY_LINEARS) == GO1_POLICY_LAYERS
 N_ADAPT_LINEARS = 3
 # the MLP height-map encoder's Linear layers (rollout_cnn.HeightMapEncoder.model), in front of the heads
 ENCODER_LINEARS = (("height_map_encoder.model", 0), ("height_map_encoder.model", 2))
+# the CNN height-map encoder's layers: Conv2d(2, 16, 3), Conv2d(16, 32, 3), Linear(3360, E)
+CONV_ENCODER_LAYERS = (("height_map_encoder.model", 0), ("height_map_encoder.model", 3),
+                       ("height_map_encoder.model", 7))
 
 
 def policy_linears(ac):

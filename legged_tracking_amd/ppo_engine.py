@@ -33,6 +33,8 @@ N_ADAPT_TENSORS = 2 * LA.N_ADAPT_LINEARS
 # adaptation loss through process_obs_history)
 ENC_PARAM_NAMES = [f"{seq}.{i}.{k}" for seq, i in LA.ENCODER_LINEARS for k in ("weight", "bias")]
 ENC_EMBEDDINGS = (128, 256, 384, 512)
+# the CNN height-map encoder's parameters (conv1, conv2, linear): the same place in the flat buffers and slices
+CONV_PARAM_NAMES = [f"{seq}.{i}.{k}" for seq, i in LA.CONV_ENCODER_LAYERS for k in ("weight", "bias")]
 
 _lib = None
 
@@ -99,6 +101,35 @@ def encoder_supported(ac):
         return False
 
 
+def conv_encoder_supported(ac):
+    """The engine's CNN encoder architecture (go1_ppo_dims.enc_mode 3): rollout_cnn.ActorCritic with use_cnn on the
+    reference's (2, 61, 31) map (the dims do not carry the map's x and y, so no other shape), Conv(2, 16, 3, pad 1)
+    ReLU MaxPool(2) Conv(16, 32, 3, pad 1) ReLU MaxPool(2) Flatten Linear(3360, E), E in ENC_EMBEDDINGS, whole
+    frames in the history, and the supported heads on policy_input_dim.  Every other shape keeps the torch update."""
+    try:
+        if not ac.use_cnn or not isinstance(ac.recurrent_latent_embedding, torch.nn.Identity):
+            return False
+        names = [n for n, _ in ac.named_parameters()]
+        model, E = ac.height_map_encoder.model, ac.cnn_num_embedding
+        if len(model) != 8 or sorted(n for n in names if n not in PARAM_NAMES) != sorted(CONV_PARAM_NAMES):
+            return False
+        nn = torch.nn
+        kinds = [type(m) for m in model] == [nn.Conv2d, nn.ReLU, nn.MaxPool2d, nn.Conv2d, nn.ReLU, nn.MaxPool2d,
+                                             nn.Flatten, nn.Linear]
+        convs = all((c.kernel_size, c.stride, c.padding, c.dilation, c.groups, c.padding_mode) ==
+                    ((3, 3), (1, 1), (1, 1), (1, 1), 1, "zeros") for c in (model[0], model[3])) if kinds else False
+        pools = all((m.kernel_size, m.stride, m.padding, m.dilation, m.ceil_mode) == (2, 2, 0, 1, False)
+                    for m in (model[2], model[5])) if kinds else False
+        shapes = [tuple(model[i].weight.shape) for i in (0, 3, 7)]
+        enc = (kinds and convs and pools and tuple(ac.height_map_shape) == LA.CNN_MAP_SHAPE
+               and shapes == [(16, 2, 3, 3), (32, 16, 3, 3), (E, LA.CNN_FEATURES)] and E in ENC_EMBEDDINGS
+               and ac.num_map <= ac.num_obs and ac.num_obs_history % ac.num_obs == 0
+               and ac.policy_input_dim == 2 * (ac.num_obs - ac.num_map) + E)
+        return enc and _heads_supported(ac, [n for n in names if n in PARAM_NAMES], ac.policy_input_dim)
+    except (AttributeError, IndexError, TypeError):
+        return False
+
+
 class PPOEngine:
     def __init__(self, alg):
         self.lib = load_library()
@@ -110,12 +141,13 @@ class PPOEngine:
         self.hist, self.priv = ac.num_obs_history, ac.num_privileged_obs
         self.na = ac.actor_body[6].out_features
         # the encoder module (encoder_supported): its parameters lead the flat buffers and the phase-1 slice
-        self.enc_dims = {}
-        if encoder_supported(ac):
-            self.enc_dims = dict(enc_mode=LA.GO1_PPO_ENC_MLP, num_obs=ac.num_obs, n_map=ac.num_map,
-                                 n_embed=ac.cnn_num_embedding)
-        self.names = (ENC_PARAM_NAMES if self.enc_dims else []) + PARAM_NAMES
-        self.n_adapt_tensors = N_ADAPT_TENSORS + (len(ENC_PARAM_NAMES) if self.enc_dims else 0)
+        self.enc_dims, enc_names = {}, []
+        if encoder_supported(ac) or conv_encoder_supported(ac):
+            self.enc_dims = dict(enc_mode=LA.GO1_PPO_ENC_CNN if ac.use_cnn else LA.GO1_PPO_ENC_MLP,
+                                 num_obs=ac.num_obs, n_map=ac.num_map, n_embed=ac.cnn_num_embedding)
+            enc_names = CONV_PARAM_NAMES if ac.use_cnn else ENC_PARAM_NAMES
+        self.names = enc_names + PARAM_NAMES
+        self.n_adapt_tensors = N_ADAPT_TENSORS + len(enc_names)
         self._stream = native.raw_stream_of(self.device)
         dims = LA.PPODims(hist=self.hist, priv=self.priv, actions=self.na, mb=1, rows=1, **self.enc_dims)
         tot, ad = C.c_int64(), C.c_int64()

@@ -843,7 +843,8 @@ class PPO:
         from . import ppo_engine
         if ppo_engine.supported(self.actor_critic):
             return True
-        if not ppo_engine.encoder_supported(self.actor_critic):
+        if not (ppo_engine.encoder_supported(self.actor_critic) or
+                ppo_engine.conv_encoder_supported(self.actor_critic)):
             return False
         from . import rollout_cnn
         return rollout_cnn.encoder_engine_on(self.actor_critic)

@@ -24,7 +24,8 @@ MI355X mapping: the rollout's forward is two HIP launches (FusedEncoderPolicy): 
 PPO update of this module runs on torch autograd, eagerly, by default (ppo_engine.supported refuses its parameter
 names, and that mini-batch step is not captured into a HIP graph).  With the MLP encoder it also runs on the HIP
 update engine (csrc/ppo_update.hip, go1_ppo_dims.enc_mode 1: one encoder pass on the last frame, captured into a
-HIP graph), switched by ENGINE_DEFAULT / GO1_PPO_ENCODER_ENGINE.
+HIP graph), switched by ENGINE_DEFAULT / GO1_PPO_ENCODER_ENGINE; with the CNN encoder on the (2, 61, 31) map
+likewise (enc_mode 3, csrc/ppo_conv.h: the conv stack's forward and backward in one kernel per direction).
 """
 import ctypes as C
 import os
@@ -43,7 +44,9 @@ ENC_HIDDEN = 256     # the MLP encoder's hidden width (actor_critic.py:49)
 # beat the module's torch eager act + evaluate at 4096 envs (tools/encoder_kernel_time.py).
 FUSED_DEFAULT = {"mlp": True, "cnn": True}
 # Which encoder modes take the HIP update engine (ppo_engine.PPOEngine with go1_ppo_dims.enc_mode) in PPO.update
-# by default.  The engine has the MLP encoder (ppo_engine.encoder_supported); the CNN's backward is not built.
+# by default.  The engine has the MLP encoder (ppo_engine.encoder_supported) and the CNN encoder on the (2, 61, 31)
+# map (ppo_engine.conv_encoder_supported, csrc/ppo_conv.h); both stay off until their update-time tables
+#  are weighed.
 # GO1_PPO_ENCODER_ENGINE=1 / 0 overrides the default for a run; GO1_PPO_ENGINE=0 switches every engine off.
 ENGINE_DEFAULT = {"mlp": False, "cnn": False}
 
