@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define GO1_ROLLOUT_ABI_VERSION 1
+#define GO1_ROLLOUT_ABI_VERSION 2
 #define GO1_OK_RT 0
 #define GO1_RT_E_ARG -1
 #define GO1_RT_E_HIP -2
@@ -64,6 +64,17 @@ typedef struct go1_transition {
  * Weights split and packed by legged_tracking_amd/rollout.py (fragment order,
  * layers: a1 a2 a3 p1 p2 p3 p4 c1 c2 c3 c4). */
 #define GO1_POLICY_LAYERS 11
+/* go1_policy_args.mode: which nets a launch runs (ABI 2).
+ *   GO1_POLICY_FULL     act + evaluate: adaptation module, actor, critic
+ *   GO1_POLICY_STUDENT  act_student (actor_critic.py:143-147): adaptation module + actor; no critic workgroup runs,
+ *                       value may be NULL and is never written, privileged_obs may be NULL; every other output is
+ *                       the bits GO1_POLICY_FULL writes for the same inputs (same Philox key and counter use)
+ *   GO1_POLICY_TEACHER  act_teacher (actor_critic.py:149-152): actor_body(cat(hist, privileged_obs)); neither the
+ *                       adaptation module nor the critic runs, the actor's latent inputs are the privileged
+ *                       observations and `latent`, when non-NULL, receives that copy; value as in STUDENT */
+#define GO1_POLICY_FULL 0
+#define GO1_POLICY_STUDENT 1
+#define GO1_POLICY_TEACHER 2
 typedef struct go1_policy_layer {
   /* [n/16][k/32][64 lanes][16] f16 (n padded to 16, k to 32): each weight w split into hi = f16(w)
      and lo = f16(w - hi); record (t, g, lane = 16 q + m) = hi, then lo, of W[16 t + m][32 g + 8 q + r],
@@ -77,7 +88,7 @@ typedef struct go1_policy_args {
   const float* obs_history;    /* (n, hist_dim) */
   const float* privileged_obs; /* (n, num_priv) */
   float* action_mean;          /* (n, num_actions) */
-  float* value;                /* (n) */
+  float* value;                /* (n); mode != GO1_POLICY_FULL: may be NULL, never written */
   float* latent;               /* (n, num_priv) or NULL: the adaptation module's output */
   /* optional in-kernel Normal(mean, std).sample() + log_prob (NULL actions = skip) */
   const float* std;            /* (num_actions) */
@@ -96,6 +107,8 @@ typedef struct go1_policy_args {
   int32_t* overflow;           /* optional: += workgroups that recomputed in f32 (the range guard) */
   go1_policy_layer layers[GO1_POLICY_LAYERS];
   int64_t hist_ld;             /* row stride of obs_history in floats (0: hist_dim; >= hist_dim) */
+  int32_t mode;                /* GO1_POLICY_FULL / STUDENT / TEACHER; anything else is GO1_RT_E_ARG.  The range guard's
+                                  f32 recomputation and `overflow` cover the nets the mode runs */
 } go1_policy_args;
 
 /* Height-map encoder of go1_gym_learn/ppo_cse_cnn (actor_critic.py:27-62, 180-198; csrc/encoder.hip): from the

@@ -19,7 +19,7 @@ STEP_FLAGS = ["-fno-slp-vectorize"]
 # name -> (sources, extra flags); the headers a library depends on are derived from its sources (lib_files)
 LIBS = {
     "libgo1_mi355x.so": (["go1_step.hip", "go1_terrain.hip"], STEP_FLAGS),
-    "libgo1_rollout.so": (["rollout.hip", "encoder.hip"], []),
+    "libgo1_rollout.so": (["rollout.hip", "policy_actor.hip", "encoder.hip"], []),
     "libgo1_ppo.so": (["ppo_update.hip"], []),
     # kernel-argument preloading: the curriculum launch's leading scalar arguments arrive in SGPRs with the wave
     # (11.75-11.78 against 12.02-12.10 us average per launch, alternating runs of one session)

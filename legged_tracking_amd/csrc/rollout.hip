@@ -20,24 +20,10 @@
 #include <string>
 
 #include "../../include/go1_rollout.h"
+#include "policy_tiles.h"
 #include "split_mfma.h"
 
 namespace {
-
-// Philox4x32-10 (Salmon et al. 2011), as in the env step kernel
-__device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = (uint32_t)p1;
-    c[3] = (uint32_t)p0;
-    c[0] = n0;
-    c[2] = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
 
 thread_local std::string g_err;
 
@@ -225,205 +211,11 @@ __global__ __launch_bounds__(256) void record_flat_kernel(RecPlan P, go1_transit
   }
 }
 
-// ------------------------------------------------------------------ policy inference
-// ActorCritic.act / evaluate (actor_critic.py:121-150) for 16 envs per workgroup of 16 waves:
-//   adaptation: hist(261) -> 256 -> 128 -> 2 (latent)
-//   actor:      [hist, latent](263) -> 512 -> 256 -> 128 -> 12 (action mean)
-//   critic:     [hist, priv](263)   -> 512 -> 256 -> 128 -> 1  (value)
-// ELU between layers.  f32 accuracy from f16 matrix cores ("3xF16"): every f32 weight and
-// activation x is split into hi = f16(x) and lo = f16(x - hi) (22 significant bits together),
-// and each 32-deep K group of a dot product is three v_mfma_f32_16x16x32_f16,
-//   acc += Whi Xhi + Whi Xlo + Wlo Xhi
-// with products exact in f32 and f32 accumulation; the dropped Wlo Xlo term is ~2^-22 of the
-// product, below the f32 rounding of the sums.  On gfx950 a 16x16x32 f16 MFMA issues in the 16
-// cycles of a 16x16x16 one (tools/probes/mfma_rate.hip: 16.3 cycles each, one wave), so the K=32 form
-// does twice the work per MFMA cycle.  Weights are split and packed on the host into fragment order:
-// 32 bytes per lane per (tile, K group) = 8 hi + 8 lo halves, L2-resident (2.8 MB for all three
-// nets).  Activations live in LDS already split, as [k/8][env][8] halves (hi plane, then lo plane): a
-// B fragment (k = 32 g + 8 q + r, env c) is one 16-byte read per plane, and a layer's output tile
-// (rows 4 q + r of env c) one 8-byte write.
-constexpr int PIN = 288;  // 261 / 263 inputs padded to a multiple of 32
-constexpr int PW = 16;    // waves per workgroup (four per SIMD)
-
-typedef go1_policy_layer PolicyLayer;  // w packed [n/16][k/32][64 lanes][8 hi + 8 lo halves], b [n padded to 16]
-
-// split activation planes in LDS: element (k, env c) at [k / 8][c][k % 8] of hi, and of lo
-struct ActV {
-  h8_t* hi;
-  h8_t* lo;
-};
-template <int K>
-struct Act {
-  h8_t hi[K / 8][16];
-  h8_t lo[K / 8][16];
-  __device__ ActV v() { return ActV{&hi[0][0], &lo[0][0]}; }
-};
-
-// Normal(0, 1) draws of actions 4 q .. 4 q + 3 of global env gid: one Philox4x32-10 block keyed by
-// (env, action group, step), two Box-Muller pairs on the hardware log2 / sqrt / sin / cos (v_sin / v_cos
-// take revolutions).  The samples are the kernel's own stream (the reference draws from torch's generator).
-__device__ __forceinline__ void normal4(uint32_t gid, int q, uint64_t step, uint64_t seed, float z[4]) {
-  uint32_t ctr[4] = {gid, (uint32_t)q, (uint32_t)step, (uint32_t)(step >> 32)};
-  philox4x32(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const float u1 = ((float)(ctr[2 * p] >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
-    const float u2 = (float)(ctr[2 * p + 1] >> 8) * (1.0f / 16777216.0f);       // [0, 1)
-    const float r = __builtin_amdgcn_sqrtf(-2.0f * 0.69314718055994531f * __builtin_amdgcn_logf(u1));
-    z[2 * p] = r * __builtin_amdgcn_cosf(u2);
-    z[2 * p + 1] = r * __builtin_amdgcn_sinf(u2);
-  }
-}
-
-// four consecutive features 4 kq .. 4 kq + 3 of env c, split into the two planes
-__device__ __forceinline__ void act_store4(ActV d, int kq, int c, f4_t v, int* ovf) {
-  h4_t h, l;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    ovf_check(v[r], ovf);
-    h[r] = (_Float16)v[r];
-    l[r] = (_Float16)(v[r] - (float)h[r]);
-  }
-  reinterpret_cast<h4_t*>(d.hi)[((kq >> 1) * 16 + c) * 2 + (kq & 1)] = h;
-  reinterpret_cast<h4_t*>(d.lo)[((kq >> 1) * 16 + c) * 2 + (kq & 1)] = l;
-}
-__device__ __forceinline__ void act_store1(ActV d, int k, int c, float v, int* ovf) {
-  ovf_check(v, ovf);
-  const _Float16 h = (_Float16)v;
-  reinterpret_cast<_Float16*>(d.hi)[((k >> 3) * 16 + c) * 8 + (k & 7)] = h;
-  reinterpret_cast<_Float16*>(d.lo)[((k >> 3) * 16 + c) * 8 + (k & 7)] = (_Float16)(v - (float)h);
-}
-
-template <int NT, int NL>
-__device__ __forceinline__ void policy_load(const PolicyLayer* L, int G, int g, int tile0, int tstride, int lane,
-                                            f8_t (&w)[NL][NT]) {
-#pragma unroll
-  for (int l = 0; l < NL; ++l)
-#pragma unroll
-    for (int i = 0; i < NT; ++i)
-      w[l][i] = reinterpret_cast<const f8_t*>(L[l].w)[((size_t)(tile0 + i * tstride) * G + g) * 64 + lane];
-  // keep the prefetch where it is written: otherwise the scheduler sinks the loads next to
-  // their MFMAs and the waits become vmcnt(1), exposing the L2 latency every group
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// the first D weight groups of a policy_tiles_e phase, issued early: they depend on nothing the
-// workgroup computes, so the adaptation module's can be in flight while the inputs are staged
-template <int NT, int NL, int G, int D>
-__device__ __forceinline__ void policy_prefetch(const PolicyLayer* L, int tile0, int tstride, int lane,
-                                                f8_t (&w)[D][NL][NT]) {
-#pragma unroll
-  for (int g = 0; g < D && g < G; ++g) policy_load<NT, NL>(L, G, g, tile0, tstride, lane, w[g]);
-}
-
-// NT output tiles (tile0 + i * tstride) of NL layers at the same depth (the actor and the critic
-// advance together) for ET env tiles of 16 envs that share every weight fragment (src / dst [et][l]):
-// acc = b + W x, ELU (act), store split to dst.  The G K groups are unrolled and the weight fragments
-// run D groups ahead of the MFMAs: with three 8-cycle f16 MFMAs per fragment the layers are bound by
-// the L2 -> CU weight stream, which needs ~12 16-byte loads in flight per lane (64 B/clk/CU x the L2
-// latency, 16 waves).
-template <int NT, int NL, int ET>
-__device__ __forceinline__ void policy_group_e(const f8_t (&w)[NL][NT], const ActV (*src)[NL], int g, int q, int c,
-                                               f4_t (&acc)[ET][NL][NT]) {
-#pragma unroll
-  for (int l = 0; l < NL; ++l)
-#pragma unroll
-    for (int et = 0; et < ET; ++et) {
-      const h8_t xh = src[et][l].hi[(4 * g + q) * 16 + c], xl = src[et][l].lo[(4 * g + q) * 16 + c];
-#pragma unroll
-      for (int i = 0; i < NT; ++i) acc[et][l][i] = mfma3(w[l][i], xh, xl, acc[et][l][i]);
-    }
-}
-
-template <int NT, int NL, int ET, int G, int D, bool PREFETCHED = false>
-__device__ __forceinline__ void policy_tiles_e(const PolicyLayer* L, const ActV (*src)[NL], int tile0, int tstride,
-                                               const ActV (*dst)[NL], bool act, int lane, int* ovf,
-                                               f8_t (*pre)[NL][NT] = nullptr) {
-  const int q = lane >> 4, c = lane & 15;
-  f4_t acc[ET][NL][NT];
-  f8_t w[D][NL][NT];
-#pragma unroll
-  for (int l = 0; l < NL; ++l)
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-      const f4_t b = *reinterpret_cast<const f4_t*>(L[l].b + 16 * (tile0 + i * tstride) + 4 * q);
-#pragma unroll
-      for (int et = 0; et < ET; ++et) acc[et][l][i] = b;
-    }
-  if constexpr (PREFETCHED) {
-#pragma unroll
-    for (int g = 0; g < D; ++g)
-#pragma unroll
-      for (int l = 0; l < NL; ++l)
-#pragma unroll
-        for (int i = 0; i < NT; ++i) w[g][l][i] = pre[g][l][i];
-  } else {
-    policy_prefetch<NT, NL, G, D>(L, tile0, tstride, lane, w);
-  }
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    policy_group_e<NT, NL, ET>(w[g % D], src, g, q, c, acc);
-    if (g + D < G) policy_load<NT, NL>(L, G, g + D, tile0, tstride, lane, w[g % D]);
-  }
-#pragma unroll
-  for (int et = 0; et < ET; ++et)
-#pragma unroll
-    for (int l = 0; l < NL; ++l)
-#pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        f4_t v = acc[et][l][i];
-        if (act) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = elu(v[r]);
-        }
-        act_store4(dst[et][l], 4 * (tile0 + i * tstride) + q, c, v, ovf);
-      }
-}
-
-// the NG weight fragments of a tile_partial_e, loaded ahead (they depend on nothing the workgroup computes)
-template <int NG>
-__device__ __forceinline__ void partial_load(const PolicyLayer& L, int Gs, int tile, int g0, int lane, f8_t (&w)[NG]) {
-#pragma unroll
-  for (int i = 0; i < NG; ++i) w[i] = reinterpret_cast<const f8_t*>(L.w)[((size_t)tile * Gs + g0 + i) * 64 + lane];
-}
-
-// Partial products of one output tile over K groups [g0, g0 + NG) for ET env tiles, no bias: the
-// K-split form of the narrow layers (one wave walking all of K would run a serial MFMA chain behind
-// one L2 round trip per group).  All NG weight fragments are loaded up front (one round trip), or
-// taken from `pre`.
-template <int NG, int ET>
-__device__ __forceinline__ void tile_partial_e(const PolicyLayer& L, int Gs, int tile, int g0, const ActV* src, int lane,
-                                               f4_t (&acc)[ET], const f8_t* pre = nullptr) {
-  const int q = lane >> 4, c = lane & 15;
-  f8_t w[NG];
-  if (pre) {
-#pragma unroll
-    for (int i = 0; i < NG; ++i) w[i] = pre[i];
-  } else {
-    partial_load<NG>(L, Gs, tile, g0, lane, w);
-  }
-#pragma unroll
-  for (int et = 0; et < ET; ++et) acc[et] = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int i = 0; i < NG; ++i)
-#pragma unroll
-    for (int et = 0; et < ET; ++et)
-      acc[et] = mfma3(w[i], src[et].hi[(4 * (g0 + i) + q) * 16 + c], src[et].lo[(4 * (g0 + i) + q) * 16 + c], acc[et]);
-}
-
-// ---------------------------------------------------------------- range guard: f32 fallback
-// y = act(W x + b) for one env, W (n_out, k_in) row-major f32, by the workgroup (output o on thread o)
-__device__ void dense_f32(const float* __restrict__ W, const float* __restrict__ b, int n_out, int k_in,
-                          const float* x, float* y, bool act) {
-  for (int o = threadIdx.x; o < n_out; o += blockDim.x) {
-    float acc = b[o];
-    const float* w = W + (size_t)o * k_in;
-    for (int k = 0; k < k_in; ++k) acc = fmaf(w[k], x[k], acc);
-    y[o] = act ? elu(acc) : acc;
-  }
-  __syncthreads();
-}
-
+// ------------------------------------------------------------------ policy inference: the kernels
+// Building blocks (activation planes, tile loops, Normal draw, f32 layers) in policy_tiles.h.  Here: policy_kernel
+// and policy_kernel_split, the two launch shapes of GO1_POLICY_FULL, and policy_kernel_split_teacher; the
+// single-workgroup kernels of GO1_POLICY_STUDENT / TEACHER are in policy_actor.hip.
+//
 // The envs [e0, e0 + ne) of a workgroup whose split activations left the f16 range, recomputed in f32
 // from the unsplit weights (layers[].wf): the adaptation module + actor (+ the Normal sample with the
 // same Philox draws) and / or the critic.  `buf`: >= hist_dim + num_priv (rounded up to 32) + 768 floats of
@@ -696,8 +488,13 @@ typedef float Scr[4][16][16];  // the output layer's K-split partials of one env
 // waits for every memory operation).  policy_kernel_split never reads global memory it writes.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-template <int ET, bool CRITIC>
+// TEACHER (with !CRITIC; GO1_POLICY_TEACHER): the actor on [history, privileged obs].  No adaptation layer runs;
+// the privileged inputs are staged as the critic's are and every L1 group runs in the chunk pass.
+template <int ET, bool CRITIC, bool TEACHER = false>
 __device__ __forceinline__ void split_body(const go1_policy_args& P, SplitLds& S, int e0, int ne, int* s_ovf) {
+  static_assert(!(CRITIC && TEACHER), "the teacher mode is the actor's");
+  constexpr bool ADAPT = !CRITIC && !TEACHER;  // the adaptation module runs in front of the net
+  constexpr bool PRIV = CRITIC || TEACHER;     // the net's last inputs are the privileged observations
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int q = lane >> 4, c = lane & 15;
   const int NP = P.num_priv;
@@ -722,7 +519,7 @@ __device__ __forceinline__ void split_body(const go1_policy_args& P, SplitLds& S
   const int GA = (H + 31) / 32, GL = (KIN + 31) / 32, gl = H / 32;
   constexpr int CG = PIN / 32;
   const int nch = (GL + CG - 1) / CG, g_last = CG * (nch - 1);
-  const int g_pass = CRITIC ? GL : gl;  // L1 groups of the chunk pass
+  const int g_pass = PRIV ? GL : gl;  // L1 groups of the chunk pass
   // the f32 staging copy (h1 is free until the L1 epilogue); one chunk: the workgroup's rows are one
   // contiguous block of ne x H floats, copied with coalesced loads from one base pointer (all of the
   // thread's in flight) before the accumulators are live
@@ -731,19 +528,19 @@ __device__ __forceinline__ void split_body(const go1_policy_args& P, SplitLds& S
   // L1 weight fragments, two groups ahead (two register sets, the group loop unrolled by two)
   f8_t wA0, wL00, wL01, wA1, wL10, wL11;
   auto load0 = [&](int g) {
-    if constexpr (!CRITIC) wA0 = reinterpret_cast<const f8_t*>(Ls[0].w)[((size_t)wave * GA + g) * 64 + lane];
+    if constexpr (ADAPT) wA0 = reinterpret_cast<const f8_t*>(Ls[0].w)[((size_t)wave * GA + g) * 64 + lane];
     wL00 = reinterpret_cast<const f8_t*>(LN[0].w)[((size_t)wave * GL + g) * 64 + lane];
     wL01 = reinterpret_cast<const f8_t*>(LN[0].w)[((size_t)(wave + PW) * GL + g) * 64 + lane];
   };
   auto load1 = [&](int g) {
-    if constexpr (!CRITIC) wA1 = reinterpret_cast<const f8_t*>(Ls[0].w)[((size_t)wave * GA + g) * 64 + lane];
+    if constexpr (ADAPT) wA1 = reinterpret_cast<const f8_t*>(Ls[0].w)[((size_t)wave * GA + g) * 64 + lane];
     wL10 = reinterpret_cast<const f8_t*>(LN[0].w)[((size_t)wave * GL + g) * 64 + lane];
     wL11 = reinterpret_cast<const f8_t*>(LN[0].w)[((size_t)(wave + PW) * GL + g) * 64 + lane];
   };
   // the first chunk's first two groups are requested before the inputs: they depend on nothing the workgroup
   // computes, so the weight stream starts under the input loads' latency instead of after the staging
   {
-    const int gb0 = CRITIC ? min(CG, GL) : min(gl, min(CG, GL));
+    const int gb0 = PRIV ? min(CG, GL) : min(gl, min(CG, GL));
     if (0 < gb0) load0(0);
     if (1 < gb0) load1(1);
     __builtin_amdgcn_sched_barrier(0);
@@ -777,10 +574,13 @@ __device__ __forceinline__ void split_body(const go1_policy_args& P, SplitLds& S
   // passes read them from there)
   float* pflat = flat + ET * 16 * PIN;
   static_assert(ET * 16 * (PIN + 8) * sizeof(float) <= sizeof(SplitLds::h1), "f32 staging exceeds h1");
-  if constexpr (CRITIC) {
+  if constexpr (PRIV) {
     const int t = min(tid, ET * 16 * NP - 1), e = t / NP;
     const float x = P.privileged_obs[(size_t)(e0 + min(e, ne - 1)) * NP + (t - e * NP)];
     if (tid < ET * 16 * NP) pflat[tid] = x;
+    if constexpr (TEACHER) {  // policy_info["latents"] = privileged_info: the rows are one contiguous block
+      if (P.latent && tid < ne * NP) P.latent[(size_t)e0 * NP + tid] = x;
+    }
   }
   f4_t accA[ET], accL[ET][2];
   {
@@ -790,7 +590,7 @@ __device__ __forceinline__ void split_body(const go1_policy_args& P, SplitLds& S
 #pragma unroll
       for (int et = 0; et < ET; ++et) accL[et][i] = b;
     }
-    if constexpr (!CRITIC) {
+    if constexpr (ADAPT) {
       const f4_t b = *reinterpret_cast<const f4_t*>(Ls[0].b + 16 * wave + 4 * q);
 #pragma unroll
       for (int et = 0; et < ET; ++et) accA[et] = b;
@@ -839,7 +639,7 @@ __device__ __forceinline__ void split_body(const go1_policy_args& P, SplitLds& S
           float x = 0.0f;
           if (e < ne) {
             if (k < H) x = flat[e * fs + kl];
-            else if (CRITIC && k < KIN) x = pflat[e * NP + (k - H)];
+            else if (PRIV && k < KIN) x = pflat[e * NP + (k - H)];
           }
           ovf_check(x, s_ovf);
           hi8[r] = (_Float16)x;
@@ -854,12 +654,12 @@ __device__ __forceinline__ void split_body(const go1_policy_args& P, SplitLds& S
     // the chunk's groups (uniform runtime bounds, no predicated MFMAs): [g0, gb) feed the adaptation
     // module (actor) and L1; the next group's fragments are requested before this group's MFMAs
     {
-      const int g1 = min(g0 + CG, GL), gb = CRITIC ? g1 : min(gl, g1);
+      const int g1 = min(g0 + CG, GL), gb = PRIV ? g1 : min(gl, g1);
       auto group = [&](int gi, const f8_t& a, const f8_t& l0, const f8_t& l1) {
 #pragma unroll
         for (int et = 0; et < ET; ++et) {
           const h8_t xh = S.xin[et].hi[4 * gi + q][c], xl = S.xin[et].lo[4 * gi + q][c];
-          if constexpr (!CRITIC) accA[et] = mfma3(a, xh, xl, accA[et]);
+          if constexpr (ADAPT) accA[et] = mfma3(a, xh, xl, accA[et]);
           accL[et][0] = mfma3(l0, xh, xl, accL[et][0]);
           accL[et][1] = mfma3(l1, xh, xl, accL[et][1]);
         }
@@ -876,7 +676,7 @@ __device__ __forceinline__ void split_body(const go1_policy_args& P, SplitLds& S
           if (g + 3 < gb) load1(g + 3);
         }
       }
-      if constexpr (!CRITIC) {  // the history's last, partial group (adaptation module only; the actor's
+      if constexpr (ADAPT) {  // the history's last, partial group (adaptation module only; the actor's
         if (GA > gl && gl >= g0 && gl < g1) {  // L1 takes it with the latent)
           const f8_t a = reinterpret_cast<const f8_t*>(Ls[0].w)[((size_t)wave * GA + gl) * 64 + lane];
 #pragma unroll
@@ -890,7 +690,7 @@ __device__ __forceinline__ void split_body(const go1_policy_args& P, SplitLds& S
   // no barrier: the copy in h1 was last read before the last chunk's MFMAs (every wave has passed that
   // barrier), so each wave stores its first-layer outputs as soon as its own MFMAs are done, overlapping the
   // other waves' MFMAs (a barrier here made every wave run its ELUs at the same time)
-  if constexpr (!CRITIC) {
+  if constexpr (ADAPT) {
     // adaptation module epilogue: ELU, split into h1 rows 0-255
 #pragma unroll
     for (int et = 0; et < ET; ++et) {
@@ -1075,7 +875,10 @@ __device__ __forceinline__ void split_body(const go1_policy_args& P, SplitLds& S
   }
   PSTAMP(8);
   __syncthreads();
-  if (*s_ovf) policy_fallback(P, e0, ne, !CRITIC, CRITIC, reinterpret_cast<float*>(&S.h1[0]));
+  if (*s_ovf) {
+    if constexpr (TEACHER) policy_fallback_actor<true>(P, e0, ne, reinterpret_cast<float*>(&S.h1[0]));
+    else policy_fallback(P, e0, ne, !CRITIC, CRITIC, reinterpret_cast<float*>(&S.h1[0]));
+  }
 }
 
 // envs per workgroup: actor workgroups (adaptation module + actor, 1.6 MB of split weights) take SPLIT_ET_A
@@ -1084,6 +887,7 @@ __device__ __forceinline__ void split_body(const go1_policy_args& P, SplitLds& S
 constexpr int SPLIT_ET_A = 2, SPLIT_ET_C = 3;
 constexpr int SE_A = 16 * SPLIT_ET_A, SE_C = 16 * SPLIT_ET_C;
 
+// GO1_POLICY_STUDENT is this kernel launched with its actor workgroups only.
 __global__ __launch_bounds__(64 * PW) void policy_kernel_split(go1_policy_args P) {
   __shared__ SplitLds S;
   __shared__ int s_ovf;
@@ -1097,6 +901,17 @@ __global__ __launch_bounds__(64 * PW) void policy_kernel_split(go1_policy_args P
     const int e0 = (blockIdx.x - na) * SE_C;
     split_body<SPLIT_ET_C, true>(P, S, e0, min(SE_C, P.n_envs - e0), &s_ovf);
   }
+}
+
+// GO1_POLICY_TEACHER: ceil(n / SE_A) workgroups of the actor on [history, privileged obs] (a kernel of its own:
+// policy_kernel_split's code is what it was without the modes)
+__global__ __launch_bounds__(64 * PW) void policy_kernel_split_teacher(go1_policy_args P) {
+  __shared__ SplitLds S;
+  __shared__ int s_ovf;
+  PSTAMP(0);
+  if (threadIdx.x == 0) s_ovf = 0;
+  const int e0 = blockIdx.x * SE_A;
+  split_body<SPLIT_ET_A, false, true>(P, S, e0, min(SE_A, P.n_envs - e0), &s_ovf);
 }
 
 }  // namespace
@@ -1146,6 +961,9 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restri
   for (; p < P; ++p) acc += partial[(int64_t)p * C + c];
   out[c] = acc;
 }
+
+// policy_actor.hip: variant 1 of GO1_POLICY_STUDENT / TEACHER
+hipError_t go1_policy_launch_actor(const go1_policy_args& P, hipStream_t stream);
 
 // the library's error record for its other sources (encoder.hip)
 int go1_rt_fail(int code, const std::string& m) { return fail(code, m); }
@@ -1234,9 +1052,16 @@ int go1_gae(const float* rewards, const uint8_t* dones, const float* values, con
 }
 
 int go1_policy_forward(const go1_policy_args* args, void* stream) {
-  if (!args || args->n_envs <= 0 || !args->obs_history || !args->privileged_obs || !args->action_mean ||
-      !args->value)
+  if (!args || args->n_envs <= 0 || !args->obs_history || !args->action_mean)
     return fail(GO1_RT_E_ARG, "go1_policy_forward: bad argument");
+  if (args->mode != GO1_POLICY_FULL && args->mode != GO1_POLICY_STUDENT && args->mode != GO1_POLICY_TEACHER)
+    return fail(GO1_RT_E_ARG, "go1_policy_forward: mode " + std::to_string(args->mode) +
+                                  " is none of GO1_POLICY_FULL (0), GO1_POLICY_STUDENT (1), GO1_POLICY_TEACHER (2)");
+  // the critic's inputs and output (FULL), the teacher's latent inputs
+  if ((args->mode != GO1_POLICY_STUDENT && !args->privileged_obs) || (args->mode == GO1_POLICY_FULL && !args->value))
+    return fail(GO1_RT_E_ARG, "go1_policy_forward: bad argument");
+  if (args->actions && (!args->std || !args->action_sigma || !args->log_prob))
+    return fail(GO1_RT_E_ARG, "go1_policy_forward: actions needs std, action_sigma and log_prob");
   if (args->num_priv < 1 || args->num_priv > 8 || args->hist_dim < 1 || args->num_actions > 16)
     return fail(GO1_RT_E_ARG, "go1_policy_forward: input / latent / action width outside the compiled architecture");
   {
@@ -1262,11 +1087,20 @@ int go1_policy_forward(const go1_policy_args* args, void* stream) {
     return fail(GO1_RT_E_ARG, "go1_policy_forward: hist_ld < hist_dim");
   go1_policy_args P = *args;
   if (P.hist_ld == 0) P.hist_ld = P.hist_dim;
-  if (P.variant == 0)
-    hipLaunchKernelGGL(policy_kernel_split, dim3((P.n_envs + SE_A - 1) / SE_A + (P.n_envs + SE_C - 1) / SE_C),
-                       dim3(64 * PW), 0, (hipStream_t)stream, P);
-  else
-    hipLaunchKernelGGL(policy_kernel, dim3((P.n_envs + 15) / 16), dim3(64 * PW), 0, (hipStream_t)stream, P);
+  const hipStream_t s = (hipStream_t)stream;
+  const dim3 block(64 * PW), g16((P.n_envs + 15) / 16), ga((P.n_envs + SE_A - 1) / SE_A);
+  if (P.variant == 0) {
+    if (P.mode == GO1_POLICY_FULL)
+      hipLaunchKernelGGL(policy_kernel_split, dim3(ga.x + (P.n_envs + SE_C - 1) / SE_C), block, 0, s, P);
+    else if (P.mode == GO1_POLICY_STUDENT)  // the actor workgroups only
+      hipLaunchKernelGGL(policy_kernel_split, ga, block, 0, s, P);
+    else
+      hipLaunchKernelGGL(policy_kernel_split_teacher, ga, block, 0, s, P);
+  } else if (P.mode == GO1_POLICY_FULL) {
+    hipLaunchKernelGGL(policy_kernel, g16, block, 0, s, P);
+  } else {
+    RT_TRY(go1_policy_launch_actor(P, s));
+  }
   RT_TRY(hipGetLastError());
   return GO1_OK_RT;
 }

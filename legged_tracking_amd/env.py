@@ -73,6 +73,10 @@ class EpisodeLogRing:
         self.cuda = device.type == "cuda"
         self.compact = compact and self.cuda
         self.dropped = 0  # compact rows the device had no room for (counted, never silently lost)
+        # optional listener(rows (m, W) f32, env ids (m,), step tags (m,)): every finished train-env episode in log
+        # order (step, then env), before the deques' 4000-entry cut drops the env ids and the older rows.  Called
+        # whenever rows are processed (a drain at the latest); a tag orders the rows of one call.  evaluate.py's.
+        self.listener = None
         if self.compact:
             # Rows of one half: the resets of R steps.  Every env resetting on every step would need
             # R x n rows (300 MB of (W + 2)-float rows per half at 256 k envs); the cap allows a quarter
@@ -226,6 +230,8 @@ class EpisodeLogRing:
         pos = np.searchsorted(tail, tag[sel])
         to[pos, eid[sel]] = rows[sel, ns] > np.float32(env.max_episode_length)
         env._timeouts.extend(to.reshape(-1)[-4000:])
+        if self.listener is not None:
+            self.listener(rows[:, :W], eid, tag)
         self._extend(rows[-4000:])
 
     def _extend(self, rows):
@@ -245,6 +251,8 @@ class EpisodeLogRing:
         steps, envs = np.nonzero(col > 0)                    # by step, then env
         if steps.size == 0:
             return
+        if self.listener is not None:
+            self.listener(logs[steps, envs], envs, steps)
         rows = logs[steps, envs][-4000:]
         reset_steps = np.unique(steps)
         timeouts = (col[reset_steps] > np.float32(env.max_episode_length)).reshape(-1)[-4000:]

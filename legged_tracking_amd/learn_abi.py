@@ -6,13 +6,14 @@ go1_ppo_abi_sizes of the compiled libraries.
 """
 import ctypes as C
 
-GO1_ROLLOUT_ABI_VERSION = 1
+GO1_ROLLOUT_ABI_VERSION = 2
 GO1_PPO_ABI_VERSION = 2
 GO1_POLICY_LAYERS = 11
 GO1_PPO_AUX = 8
 GO1_ENCODER_LAYERS = 3
 GO1_ENC_MLP, GO1_ENC_CNN = 0, 1
 GO1_ENC_MAX_EMBED = 512
+GO1_POLICY_FULL, GO1_POLICY_STUDENT, GO1_POLICY_TEACHER = 0, 1, 2  # go1_policy_args.mode
 GO1_PPO_ENC_NONE, GO1_PPO_ENC_MLP = 0, 1  # go1_ppo_dims.enc_mode
 GO1_PPO_ENC_CNN = 3  # 2 stays refused (go1_ppo.h)
 CNN_MAP_SHAPE, CNN_FEATURES = (2, 61, 31), 3360  # the one map the engine's CNN mode takes, its twice-pooled size
@@ -42,7 +43,7 @@ class PolicyArgs(C.Structure):  # go1_policy_args
                 ("std", P), ("actions", P), ("action_sigma", P), ("log_prob", P), ("rng_seed", C.c_uint64),
                 ("rng_step", C.c_uint64), ("env_id_offset", I32), ("n_envs", I32), ("hist_dim", I32),
                 ("num_actions", I32), ("num_priv", I32), ("variant", I32), ("overflow", P),
-                ("layers", PolicyLayer * GO1_POLICY_LAYERS), ("hist_ld", I64)]
+                ("layers", PolicyLayer * GO1_POLICY_LAYERS), ("hist_ld", I64), ("mode", I32)]
 
 
 class EncoderArgs(C.Structure):  # go1_encoder_args

@@ -165,27 +165,34 @@ class FusedPolicy:
             self.args.layers[i].w, self.args.layers[i].b = w.data_ptr(), b.data_ptr()
             self.args.layers[i].wf = self.wf[i].data_ptr()
 
-    def forward(self, obs_history, privileged_obs, sample=None):
+    def forward(self, obs_history, privileged_obs, sample=None, mode=0):
         """-> (mean, value, latent) or, with sample = (rng_seed, rng_step, env_id_offset),
-        (mean, value, latent, actions, sigma, log_prob): Normal(mean, std) drawn in-kernel."""
+        (mean, value, latent, actions, sigma, log_prob): Normal(mean, std) drawn in-kernel.
+
+        mode (go1_policy_args.mode): 0 act + evaluate; 1 act_student (no critic: value is None, privileged_obs
+        may be None); 2 act_teacher (the actor on [history, privileged_obs]; latent is the copy of
+        privileged_obs that policy_info["latents"] gets)."""
         if self.packed is None:
             self.pack()
         h = obs_history.detach()
-        p = privileged_obs.detach()
         if h.dim() != 2 or h.stride(1) != 1 or h.stride(0) < h.shape[1]:
             h = h.contiguous()  # row-strided windows (the velocity env's history) are read in place
-        if not p.is_contiguous():
-            p = p.contiguous()
+        p = None
+        if privileged_obs is not None:
+            p = privileged_obs.detach()
+            if not p.is_contiguous():
+                p = p.contiguous()
         n = h.shape[0]
         na = self.na
         dev = h.device
         mean = torch.empty(n, na, device=dev)
-        value = torch.empty(n, 1, device=dev)
+        value = torch.empty(n, 1, device=dev) if mode == LA.GO1_POLICY_FULL else None
         latent = torch.empty(n, self.np, device=dev)
         a = self.args
-        a.variant = self.variant
-        a.obs_history, a.privileged_obs = h.data_ptr(), p.data_ptr()
-        a.action_mean, a.value, a.latent = mean.data_ptr(), value.data_ptr(), latent.data_ptr()
+        a.variant, a.mode = self.variant, mode
+        a.obs_history, a.privileged_obs = h.data_ptr(), p.data_ptr() if p is not None else None
+        a.action_mean, a.latent = mean.data_ptr(), latent.data_ptr()
+        a.value = value.data_ptr() if value is not None else None
         a.n_envs, a.hist_dim, a.hist_ld = n, h.shape[1], h.stride(0)
         out = (mean, value, latent)
         if sample is not None:
@@ -347,19 +354,20 @@ class ActorCritic(nn.Module):
 
     is_recurrent = False
 
-    def __init__(self, num_obs, num_privileged_obs, num_obs_history, num_actions, **kwargs):
+    def __init__(self, num_obs, num_privileged_obs, num_obs_history, num_actions, ac_args=None, **kwargs):
         super().__init__()
-        self.decoder = AC_Args.use_decoder
+        A = self.ac_args = AC_Args if ac_args is None else ac_args  # a copy: checkpoint.load_actor_critic
+        self.decoder = A.use_decoder
         self.num_obs_history = num_obs_history
         self.num_privileged_obs = num_privileged_obs
-        act = get_activation(AC_Args.activation)
-        self.adaptation_module = _mlp([num_obs_history, *AC_Args.adaptation_module_branch_hidden_dims,
+        act = get_activation(A.activation)
+        self.adaptation_module = _mlp([num_obs_history, *A.adaptation_module_branch_hidden_dims,
                                        num_privileged_obs], act)
-        self.actor_body = _mlp([num_privileged_obs + num_obs_history, *AC_Args.actor_hidden_dims, num_actions], act)
-        self.critic_body = _mlp([num_privileged_obs + num_obs_history, *AC_Args.critic_hidden_dims, 1], act)
-        self.std = nn.Parameter(AC_Args.init_noise_std * torch.ones(num_actions))
+        self.actor_body = _mlp([num_privileged_obs + num_obs_history, *A.actor_hidden_dims, num_actions], act)
+        self.critic_body = _mlp([num_privileged_obs + num_obs_history, *A.critic_hidden_dims, 1], act)
+        self.std = nn.Parameter(A.init_noise_std * torch.ones(num_actions))
         self.distribution = None
-        self.normalize_obs = AC_Args.normalize_obs
+        self.normalize_obs = A.normalize_obs
         if self.normalize_obs:
             raise NotImplementedError("normalize_obs is off in the README configuration and not on this path")
 
@@ -423,6 +431,65 @@ class ActorCritic(nn.Module):
     def adaptation_pred_train(self, observation_history):
         """The adaptation step's prediction (ppo.py:170)."""
         return _mlp_train(self.adaptation_module, observation_history)
+
+
+# ----------------------------------------------------------------------------- inference policies
+_NO_INFO = {}  # policy(ob) without a policy_info: nothing is copied to the host for it
+
+
+class InferencePolicy:
+    """What fused_inference returns: policy(ob, policy_info={}) -> actions, act_inference / act_expert's signature
+    (actor_critic.py:137-152).  `fused` is the FusedPolicy / FusedEncoderPolicy it runs on, or None (the module's
+    own act_student / act_teacher)."""
+
+    def __init__(self, ac, fused, teacher, sample):
+        self.ac, self.fused, self.teacher = ac, fused, bool(teacher)
+        self.mode = LA.GO1_POLICY_TEACHER if teacher else LA.GO1_POLICY_STUDENT
+        self.seed = None if sample is None else int(sample)
+        self.step = 0  # the Philox counter: one value per call
+        self._gen = None
+
+    def pack(self):
+        """Re-pack the kernels' weight copies (after the module's parameters changed)."""
+        if self.fused is not None:
+            self.fused.pack()
+
+    def __call__(self, ob, policy_info=_NO_INFO):
+        hist, priv = ob["obs_history"], ob.get("privileged_obs")
+        want_info = policy_info is not _NO_INFO
+        if self.fused is None:
+            with torch.no_grad():
+                info = policy_info if want_info else {}
+                mean = self.ac.act_teacher(hist, priv, policy_info=info) if self.teacher else \
+                    self.ac.act_student(hist, policy_info=info)
+                if self.seed is None:
+                    return mean
+                if self._gen is None:
+                    self._gen = torch.Generator(device=mean.device).manual_seed(self.seed)
+                return mean + self.ac.std.detach() * torch.randn(mean.shape, generator=self._gen, device=mean.device)
+        sample = None
+        if self.seed is not None:
+            self.step += 1
+            sample = (self.seed, self.step, 0)
+        out = self.fused.forward(hist, priv if self.teacher else None, sample=sample, mode=self.mode)
+        if want_info:  # as the module methods fill it
+            policy_info["latents"] = priv if self.teacher else out[2].cpu().numpy()
+        return out[0] if sample is None else out[3]
+
+
+def fused_inference(ac, teacher=False, sample=None):
+    """The student (act_inference) or teacher (act_expert) policy of `ac` as a callable
+    policy(ob, policy_info={}) -> actions, on the fused HIP kernels (go1_policy_forward in GO1_POLICY_STUDENT /
+    GO1_POLICY_TEACHER mode, behind go1_heightmap_encode for the encoder module) where
+    HipRolloutKernels.policy(ac) gives one; otherwise (a module on the CPU, an architecture the kernels do not
+    take, rollout_cnn.FUSED_DEFAULT off) on the module's own act_student / act_teacher.
+
+    sample: None returns the action mean, as act_inference / act_expert do; an int seed returns
+    Normal(mean, std) draws (in-kernel Philox keyed by the seed, one counter value per call).  The weights are
+    packed at the first call; policy.pack() re-packs them after the module's parameters changed."""
+    dev = next(ac.parameters()).device
+    fused = HipRolloutKernels().policy(ac) if dev.type == "cuda" else None
+    return InferencePolicy(ac, fused, teacher, sample)
 
 
 # ----------------------------------------------------------------------------- storage
@@ -1026,8 +1093,9 @@ class Runner:
         return "last_run/checkpoints"
 
     def save(self, save_path=None):
-        """ac_weights.pt + adaptation_module_latest.jit + body_latest.jit (__init__.py:274-319), uploaded
-        with wandb.save when logging to wandb (:294-297)."""
+        """ac_weights.pt + adaptation_module_latest.jit + body_latest.jit (__init__.py:274-319) and parameters.pkl
+        (the Cfg, which the reference pickles at construction, :81-84), uploaded with wandb.save when logging to
+        wandb (:294-297)."""
         if _world() > 1 and torch.distributed.get_rank() != 0:
             return
         save_path = save_path or self.checkpoint_dir()
@@ -1038,6 +1106,10 @@ class Runner:
         torch.save(ac.state_dict(), paths[0])
         torch.jit.script(copy.deepcopy(ac.adaptation_module).to("cpu")).save(paths[1])
         torch.jit.script(copy.deepcopy(ac.actor_body).to("cpu")).save(paths[2])
+        cfg = getattr(self.env, "cfg", None)
+        if cfg is not None:  # the run's Cfg, which play / evaluate rebuild the env from
+            from . import checkpoint
+            paths.append(checkpoint.save_parameters(cfg, save_path))
         if self.log_wandb:
             import wandb
             for path in paths:

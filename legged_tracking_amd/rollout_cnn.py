@@ -341,9 +341,9 @@ class FusedEncoderPolicy:
             native.check(self.lib, rc)
         return out
 
-    def forward(self, obs_history, privileged_obs, sample=None):
-        """FusedPolicy.forward's tuples for the encoder module."""
-        return self.heads.forward(self.encode(obs_history), privileged_obs, sample=sample)
+    def forward(self, obs_history, privileged_obs, sample=None, mode=0):
+        """FusedPolicy.forward's tuples for the encoder module (the encoder launch is the same in every mode)."""
+        return self.heads.forward(self.encode(obs_history), privileged_obs, sample=sample, mode=mode)
 
 
 def fused_policy(ac):
