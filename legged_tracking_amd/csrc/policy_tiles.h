@@ -69,8 +69,10 @@ __device__ __forceinline__ void normal4(uint32_t gid, int q, uint64_t step, uint
   philox4x32(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
-    const float u1 = ((float)(ctr[2 * p] >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
-    const float u2 = (float)(ctr[2 * p + 1] >> 8) * (1.0f / 16777216.0f);       // [0, 1)
+    // (0, 1]: from 2^23 on the + 0.5f is not representable and rounds to even, so the top mantissa gives exactly
+    // 1.0, where r = 0 and z = +-0 (never NaN); tests/normal_ref.py restates the draw
+    const float u1 = ((float)(ctr[2 * p] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float u2 = (float)(ctr[2 * p + 1] >> 8) * (1.0f / 16777216.0f);  // [0, 1)
     const float r = __builtin_amdgcn_sqrtf(-2.0f * 0.69314718055994531f * __builtin_amdgcn_logf(u1));
     z[2 * p] = r * __builtin_amdgcn_cosf(u2);
     z[2 * p + 1] = r * __builtin_amdgcn_sinf(u2);
