@@ -5,12 +5,12 @@ state dict is turned back into the module that wrote it.
                    what the reference's Runner pickles at construction (ppo_cse/__init__.py:81-84, the same in
                    ppo_cse_cnn) and scripts/eval.py:70-80 / play.load_cfg read back.  Runner.save() writes it.
   ac_weights.pt    the ActorCritic state dict.  Which learner wrote it is read off its keys (describe):
-                     no height_map_encoder.* key                    rollout.ActorCritic      (ppo_cse)
-                     a 4-D height_map_encoder.model.0.weight        rollout_cnn, CNN encoder (ppo_cse_cnn)
-                     otherwise                                      rollout_cnn, MLP encoder
+                     no height_map_encoder.* key                    actor_critic.ActorCritic (ppo_cse)
+                     a 4-D height_map_encoder.model.0.weight        ActorCriticCNN, CNN encoder (ppo_cse_cnn)
+                     otherwise                                      ActorCriticCNN, MLP encoder
 
-load_actor_critic builds the module for an env's dimensions, with an AC_Args copy (the class-level AC_Args of
-rollout / rollout_cnn are not touched), and refuses a state dict that does not fit what the Cfg implies.
+load_actor_critic builds the module for an env's dimensions, with an AC_Args copy (the class-level AC_Args and
+AC_Args_CNN of actor_critic are not touched), and refuses a state dict that does not fit what the Cfg implies.
 """
 import os
 import pickle
@@ -18,7 +18,7 @@ import pickle
 import numpy as np
 import torch
 
-from . import config as CF
+from . import actor_critic as AC, config as CF
 
 _TYPE_DICT = type.__dict__["__dict__"]
 
@@ -108,7 +108,6 @@ def load_actor_critic(logdir, cfg, num_obs, num_privileged_obs, num_obs_history,
     those of the state dict.  ValueError, naming the key, both shapes and which side says what, when the state
     dict does not fit the Cfg: the encoder's input against the grid, the heads' widths against the frame and the
     history, num_privileged_obs, num_actions."""
-    from . import rollout as R, rollout_cnn as RC
     weights = find(logdir, "ac_weights.pt")
     if weights is None:
         raise FileNotFoundError(f"no ac_weights.pt under {logdir}")
@@ -126,13 +125,13 @@ def load_actor_critic(logdir, cfg, num_obs, num_privileged_obs, num_obs_history,
     if d["kind"] == "old":
         width, why = int(num_obs_history), (f"num_obs_history = num_observation_history x num_observations = "
                                             f"{num_obs_history}, frames of {num_obs}")
-        args = type("AC_Args", (R.AC_Args,), hidden)
+        args = type("AC_Args", (AC.AC_Args,), hidden)
     else:
         g = CF.scan_grid(cfg)
         shape = (2, g["rows"], g["ny"])
         n_map = int(np.prod(shape))
         if d["kind"] == "cnn":
-            want_in, what = RC.cnn_feature_count(shape), "features of the twice-pooled map"
+            want_in, what = AC.cnn_feature_count(shape), "features of the twice-pooled map"
         else:
             want_in, what = n_map, "map values"
         if d["encoder_in"] != want_in:
@@ -147,8 +146,8 @@ def load_actor_critic(logdir, cfg, num_obs, num_privileged_obs, num_obs_history,
         width = 2 * (int(num_obs) - n_map) + d["embedding"]
         why = (f"policy input = 2 x {int(num_obs) - n_map} scalars of a {num_obs}-wide frame + the embedding of "
                f"{d['embedding']}")
-        args = type("AC_Args", (RC.AC_Args,), dict(hidden, use_cnn=d["kind"] == "cnn", height_map_shape=shape,
-                                                   cnn_num_embedding=d["embedding"]))
+        args = type("AC_Args", (AC.AC_Args_CNN,), dict(hidden, use_cnn=d["kind"] == "cnn", height_map_shape=shape,
+                                                       cnn_num_embedding=d["embedding"]))
     checks = ((ad[0], (hidden["adaptation_module_branch_hidden_dims"][0], width), why),
               (ad[-1], (npv, sd[ad[-1]].shape[1]), f"num_privileged_obs = {npv}"),
               (actor[0], (hidden["actor_hidden_dims"][0], width + npv), f"{why}, + num_privileged_obs = {npv}"),
@@ -158,8 +157,8 @@ def load_actor_critic(logdir, cfg, num_obs, num_privileged_obs, num_obs_history,
         if tuple(sd[key].shape) != tuple(want):
             raise _mismatch(key, sd[key].shape, want, side, reason)
     if d["kind"] == "old":
-        ac = R.ActorCritic(num_obs, npv, num_obs_history, na, ac_args=args)
+        ac = AC.ActorCritic(num_obs, npv, num_obs_history, na, ac_args=args)
     else:
-        ac = RC.ActorCritic(num_obs, npv, num_obs_history, na, ac_args=args)
+        ac = AC.ActorCriticCNN(num_obs, npv, num_obs_history, na, ac_args=args)
     ac.load_state_dict(sd)
     return ac.to(device).eval()

@@ -45,7 +45,7 @@ def _module(name, **attrs):
 
 
 def install(root_dir=None):
-    from . import env as E, rollout as R
+    from . import actor_critic as AC, env as E, ppo as P, runner as RN, storage as ST
 
     class TrajectoryTrackingEnv(E.TrajectoryTrackingEnv):
         def __init__(self, sim_device, headless, num_envs=None, prone=False, deploy=False, cfg=None,
@@ -62,7 +62,7 @@ def install(root_dir=None):
                 num_learning_iterations = min(num_learning_iterations, int(cap))
             return super().learn(num_learning_iterations, *a, **k)
 
-    class Runner(_Capped, R.Runner):
+    class Runner(_Capped, RN.Runner):
         pass
 
     from . import velocity as VEL, velocity_config as VC
@@ -102,19 +102,18 @@ def install(root_dir=None):
     _module("go1_gym.envs.wrappers")
     _module("go1_gym.envs.wrappers.history_wrapper", HistoryWrapper=E.HistoryWrapper)
     _module("go1_gym_learn")
-    ppo = dict(Runner=Runner, RunnerArgs=R.RunnerArgs, ActorCritic=R.ActorCritic, AC_Args=R.AC_Args,
-               PPO=R.PPO, PPO_Args=R.PPO_Args, RolloutStorage=R.RolloutStorage)
+    ppo = dict(Runner=Runner, RunnerArgs=RN.RunnerArgs, ActorCritic=AC.ActorCritic, AC_Args=AC.AC_Args,
+               PPO=P.PPO, PPO_Args=P.PPO_Args, RolloutStorage=ST.RolloutStorage)
     _module("go1_gym_learn.ppo_cse", **ppo)
     _module("go1_gym_learn.ppo_cse.actor_critic", **ppo)
     _module("go1_gym_learn.ppo_cse.ppo", **ppo)
     _module("go1_gym_learn.ppo_cse.rollout_storage", **ppo)
-    from . import rollout_cnn as RC
 
-    class RunnerCNN(_Capped, RC.Runner):
+    class RunnerCNN(_Capped, RN.RunnerCNN):
         pass
 
-    cnn = dict(ppo, Runner=RunnerCNN, ActorCritic=RC.ActorCritic, AC_Args=RC.AC_Args,
-               HeightMapEncoder=RC.HeightMapEncoder)
+    cnn = dict(ppo, Runner=RunnerCNN, ActorCritic=AC.ActorCriticCNN, AC_Args=AC.AC_Args_CNN,
+               HeightMapEncoder=AC.HeightMapEncoder)
     _module("go1_gym_learn.ppo_cse_cnn", **cnn)
     _module("go1_gym_learn.ppo_cse_cnn.actor_critic", **cnn)
     _module("go1_gym_learn.ppo_cse_cnn.ppo", **cnn)

@@ -55,7 +55,7 @@ class StepExtras(dict):
     def deferred_time_outs(self):
         """extras["time_outs"] with its pending rebinding left to the consumer: returns
         (tensor, (flag, pending, dst) device pointers or None).  The PPO record kernel resolves
-        it (rollout.py PPO.process_env_step), saving the sync launch a plain read costs."""
+        it (ppo.py PPO.process_env_step), saving the sync launch a plain read costs."""
         return self._env._deferred_time_outs()
 
     def items(self):

@@ -5,7 +5,7 @@
 Numbers for a checkpoint: the success / collision bookkeeping the reference's authors sketched in their Runner
 (ppo_cse/__init__.py:152-157), from the env's episode log.  The env is rebuilt from the checkpoint's Cfg
 (parameters.pkl; play.checkpoint_cfg) without rendering, the policy (checkpoint.load_actor_critic, either learner)
-runs through rollout.fused_inference -- the student, or with --teacher the actor on the privileged observations --
+runs through policy_kernels.fused_inference -- the student, or with --teacher the actor on the privileged observations --
 until every env has finished --episodes-per-env episodes.  --dr off applies play.DR_OFF (scripts/eval.py:89-101),
 --dr train keeps the trained ranges.  The result is one dict, printed as one JSON line (and written to --json).
 
@@ -37,7 +37,7 @@ import time
 import numpy as np
 import torch
 
-from . import config as CF, play as PL, rollout as R
+from . import config as CF, play as PL, policy_kernels as PK
 from .env import HistoryWrapper, TrajectoryTrackingEnv
 
 
@@ -174,7 +174,7 @@ def evaluate(logdir, envs=4096, episodes_per_env=1, rows=None, cols=None, terrai
     env = HistoryWrapper(TrajectoryTrackingEnv(sim_device=device, headless=True, cfg=cfg, seed=seed))
     try:
         ac = PL.load_policy_module(logdir, cfg, env)
-        policy = R.fused_inference(ac, teacher=teacher, sample=None if deterministic else seed)
+        policy = PK.fused_inference(ac, teacher=teacher, sample=None if deterministic else seed)
         table, ids, steps, dt = run_episodes(env, policy, episodes_per_env)
         out = summarize(table, ids, tuple(env.sum_keys), env.max_episode_length, env.terrain.env_tile)
         out["steps"] = int(steps)

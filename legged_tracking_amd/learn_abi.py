@@ -101,7 +101,7 @@ POLICY_LINEARS = tuple(("adaptation_module", i) for i in (0, 2, 4)) + \
                  tuple(("actor_body", i) for i in (0, 2, 4, 6)) + tuple(("critic_body", i) for i in (0, 2, 4, 6))
 assert len(POLICY_LINEARS) == GO1_POLICY_LAYERS
 N_ADAPT_LINEARS = 3
-# the MLP height-map encoder's Linear layers (rollout_cnn.HeightMapEncoder.model), in front of the heads
+# the MLP height-map encoder's Linear layers (actor_critic.HeightMapEncoder.model), in front of the heads
 ENCODER_LINEARS = (("height_map_encoder.model", 0), ("height_map_encoder.model", 2))
 # the CNN height-map encoder's layers: Conv2d(2, 16, 3), Conv2d(16, 32, 3), Linear(3360, E)
 CONV_ENCODER_LAYERS = (("height_map_encoder.model", 0), ("height_map_encoder.model", 3),

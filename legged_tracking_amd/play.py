@@ -9,7 +9,7 @@ with the domain randomisation switched off and record_all_envs on, run the polic
 (single_path without a parameters.pkl) unless --terrain names another producer.
 
 Either learner's checkpoint plays: the module is rebuilt from the state dict (checkpoint.load_actor_critic: the
-ppo_cse module, or ppo_cse_cnn's with the MLP or the CNN encoder) and driven through rollout.fused_inference, i.e.
+ppo_cse module, or ppo_cse_cnn's with the MLP or the CNN encoder) and driven through policy_kernels.fused_inference, i.e.
 go1_policy_forward in student mode (behind go1_heightmap_encode for the encoder module).  As eval.py:49,64 calls
 act(), the actions are Normal(mean, std) draws, here in-kernel and keyed by --seed; --deterministic plays the mean.
 Without a parameters.pkl a ppo_cse or MLP-encoder checkpoint plays on readme_config when its widths fit, a CNN
@@ -21,7 +21,7 @@ import pickle
 import numpy as np
 import torch
 
-from . import checkpoint as CK, config as CF, rollout as R, video
+from . import checkpoint as CK, config as CF, policy_kernels as PK, video
 from .env import HistoryWrapper, TrajectoryTrackingEnv
 
 # scripts/eval.py:89-101
@@ -117,7 +117,7 @@ def play(logdir, out, steps=500, envs=16, width=640, height=480, device="cuda:0"
     cfg = load_cfg(logdir, n_built, width, height, terrain)
     env = HistoryWrapper(TrajectoryTrackingEnv(sim_device=device, headless=True, cfg=cfg, seed=seed))
     ac = load_policy_module(logdir, cfg, env)
-    policy = R.fused_inference(ac, sample=None if deterministic else seed)
+    policy = PK.fused_inference(ac, sample=None if deterministic else seed)
     obs = env.reset()
     frames = []
     with torch.no_grad():

@@ -10,7 +10,7 @@ captured into HIP graphs after the first mini-batch (one graph at world 1; three
 gradient all-reduces at world > 1, which stay eager RCCL calls).  Hyper-parameters, the adaptive learning rate,
 the Adam step counts and the loss sums live on the device: a graph replays correctly after PPO_Args change.
 
-The torch optimizers of rollout.PPO stay the API objects (`PPO.optimizer`, `PPO.adaptation_module_optimizer`):
+The torch optimizers of ppo.PPO stay the API objects (`PPO.optimizer`, `PPO.adaptation_module_optimizer`):
 their per-parameter state entries are views of the engine's Adam state, and a state the caller loaded into them
 (`load_state_dict`) is imported before the next update.
 """
@@ -28,7 +28,7 @@ NAUX = LA.GO1_PPO_AUX
 # state_dict order of the supported ActorCritic, as the engine lays out its flat buffers (go1_ppo.h)
 PARAM_NAMES = [f"{seq}.{i}.{k}" for seq, i in LA.POLICY_LINEARS for k in ("weight", "bias")] + ["std"]
 N_ADAPT_TENSORS = 2 * LA.N_ADAPT_LINEARS
-# the MLP height-map encoder's parameters (rollout_cnn.ActorCritic): they lead the engine's flat buffers, and the
+# the MLP height-map encoder's parameters (actor_critic.ActorCriticCNN): they lead the engine's flat buffers, and the
 # adaptation optimizer's slice is encoder + adaptation module (ppo_cse_cnn/ppo.py:170-190 back-propagates the
 # adaptation loss through process_obs_history)
 ENC_PARAM_NAMES = [f"{seq}.{i}.{k}" for seq, i in LA.ENCODER_LINEARS for k in ("weight", "bias")]
@@ -81,10 +81,10 @@ def supported(ac):
 
 
 def encoder_supported(ac):
-    """The engine's encoder architecture (go1_ppo_dims.enc_mode 1): rollout_cnn.ActorCritic with the MLP encoder
+    """The engine's encoder architecture (go1_ppo_dims.enc_mode 1): actor_critic.ActorCriticCNN with the MLP encoder
     (use_cnn False; map -> 256 -> E, ELU, E in ENC_EMBEDDINGS, a map of 1..4096 values), whole frames in the
     history, and the supported heads on policy_input_dim.  supported() stays False for this module: whether its
-    update runs on the engine is rollout_cnn.ENGINE_DEFAULT / GO1_PPO_ENCODER_ENGINE's decision."""
+    update runs on the engine is ppo.ENGINE_DEFAULT / GO1_PPO_ENCODER_ENGINE's decision."""
     try:
         if ac.use_cnn or not isinstance(ac.recurrent_latent_embedding, torch.nn.Identity):
             return False
@@ -102,7 +102,7 @@ def encoder_supported(ac):
 
 
 def conv_encoder_supported(ac):
-    """The engine's CNN encoder architecture (go1_ppo_dims.enc_mode 3): rollout_cnn.ActorCritic with use_cnn on the
+    """The engine's CNN encoder architecture (go1_ppo_dims.enc_mode 3): actor_critic.ActorCriticCNN with use_cnn on the
     reference's (2, 61, 31) map (the dims do not carry the map's x and y, so no other shape), Conv(2, 16, 3, pad 1)
     ReLU MaxPool(2) Conv(16, 32, 3, pad 1) ReLU MaxPool(2) Flatten Linear(3360, E), E in ENC_EMBEDDINGS, whole
     frames in the history, and the supported heads on policy_input_dim.  Every other shape keeps the torch update."""

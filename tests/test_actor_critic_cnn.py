@@ -1,5 +1,5 @@
-"""The height-map encoder actor-critic (legged_tracking_amd/rollout_cnn.py) against the reference's
-go1_gym_learn.ppo_cse_cnn outputs (tests/golden/ppo_cnn_<case>.npz from tests/golden/make_golden_cnn.py), its
+"""The height-map encoder actor-critic (rollout_cnn.ActorCritic, legged_tracking_amd/actor_critic.py) against the
+reference's go1_gym_learn.ppo_cse_cnn outputs (tests/golden/ppo_cnn_<case>.npz from tests/golden/make_golden_cnn.py), its
 refusals, the weight packers and the C ABI of go1_heightmap_encode.  No GPU."""
 import ctypes as C
 
