@@ -26,6 +26,8 @@ LIBS = {
     "libgo1_velocity.so": (["go1_velocity.hip"], STEP_FLAGS + ["-mllvm", "-amdgpu-kernarg-preload-count=16"]),
     # the ray caster behind the recording API (render.py); it shares no file with the step libraries
     "libgo1_render.so": (["go1_render.hip"], []),
+    # the episode tracer (trace.py): a library of its own, so the render and step ABIs and their size checks stay put
+    "libgo1_trace.so": (["go1_trace.hip"], []),
     # test-only: one thin kernel per device function of go1_device.h (tests/devcheck.py), built as the step kernels are
     "libgo1_devcheck.so": (["go1_devcheck.hip"], STEP_FLAGS),
 }

@@ -468,6 +468,8 @@ class LeggedRobot(EnvBase):
                            diverged_count=self._diverged, **cf)
         if self._rec is not None:  # a recording is armed: its launch follows the step kernel on the same stream
             self._record_step(out["reset"])
+        if self._tracer is not None:
+            self._tracer.push(out["reset"], out["time_out"])
         self._last_hist = hist
         self._rng_step += 1
         self._elog.advance()
@@ -513,6 +515,8 @@ class LeggedRobot(EnvBase):
         self._train_ep["episode_length"].extend(ep)
         self._sim.reset_idx(env_ids, rng_seed=self.seed, rng_step=(1 << 62) + self._rng_step)
         self._rng_step += 1
+        if self._tracer is not None:
+            self._tracer.mark_reset(env_ids)
         tb = self.time_out_buf[: self.num_train_envs]
         self._timeouts.extend(tb.cpu().numpy())
         self._sim.extras_time_outs.copy_(tb)  # extras["time_outs"] rebinding (:289-291)

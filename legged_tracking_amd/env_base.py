@@ -301,6 +301,19 @@ class EnvBase:
     def get_complete_frames_eval(self):
         return []
 
+    # ------------------------------------------------------------------ episode tracer (trace.py)
+    # While a tracer is attached, step() issues its push launch after the step kernel (and after a recording launch):
+    # it reads the state planes and the step's reset / time_out outputs only.  With none attached nothing changes.
+    _tracer = None
+
+    def attach_tracer(self, tracer):
+        if self._tracer is not None and self._tracer is not tracer:
+            raise RuntimeError("the env already has a tracer attached (detach_tracer first)")
+        self._tracer = tracer
+
+    def detach_tracer(self):
+        self._tracer = None
+
     def render(self, mode="rgb_array"):
         """render (:1690-1699): env 0 from the follow camera, (240, 360, 4) uint8; None on the ranks that do not own
         global env 0."""

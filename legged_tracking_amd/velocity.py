@@ -445,6 +445,8 @@ class VelocityTrackingEasyEnv(EnvBase):
         self._sim.step(args)
         if self._rec is not None:  # a recording is armed: its launch follows the step's launches on the same stream
             self._record_step(self._reset[s])
+        if self._tracer is not None:
+            self._tracer.push(self._reset[s], self._time_out[s])
         self._last_hist = hist
         self._rng_step += 1
         self._slot = (s + 1) % OUT_RING
@@ -508,6 +510,8 @@ class VelocityTrackingEasyEnv(EnvBase):
         self._sim.reset_idx(env_ids, rng_seed=self.seed, rng_step=(1 << 62) + self._rng_step, log=self._log,
                             log_count=self._log_count, log_tag=self._log_tag)
         self._rng_step += 1
+        if self._tracer is not None:
+            self._tracer.mark_reset(env_ids)
         self._sim.extras_time_outs.copy_(self.time_out_buf)  # extras["time_outs"] rebinding (:251-252)
 
     def reset(self):
