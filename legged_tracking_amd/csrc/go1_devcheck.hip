@@ -166,6 +166,76 @@ extern "C" int go1dc_lanes(const float* in, float* out, int nsets, void* stream)
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// The role sums at the sizes the step kernels instantiate them with (they take their values two per swap: a lone
+// value, one pair, and the kernels' even and odd counts).  in: (nsets, DC_LANEN_VALS, 64); out: (nsets, DC_LANEN_OUTS,
+// 64), every call on the set's first N values, in the order rowsum4_n<1, 2, 6, 15>, pairsum_rows_n<1, 2, 27> (each: its
+// N lo, then its N hi), row1_bcast_n<1, 2, 27>, oddrows_sum_n<1, 2, 21>
+#define DC_LANEN_VALS 27
+#define DC_LANEN_OUTS 138
+template <int N>
+__device__ __forceinline__ void dc_load_n(const float* v, int lane, float* w) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) w[i] = v[64 * i + lane];
+}
+template <int N>
+__device__ __forceinline__ float* dc_store_n(float* o, const float* w) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) o[64 * i] = w[i];
+  return o + 64 * N;
+}
+template <int N>
+__device__ __forceinline__ float* dc_rowsum4_n(const float* v, int lane, float* o) {
+  float w[N];
+  dc_load_n<N>(v, lane, w);
+  rowsum4_n<N>(w);
+  return dc_store_n<N>(o, w);
+}
+template <int N>
+__device__ __forceinline__ float* dc_pairsum_n(const float* v, int lane, float* o) {
+  float w[N], lo[N], hi[N];
+  dc_load_n<N>(v, lane, w);
+  pairsum_rows_n<N>(w, lo, hi);
+  return dc_store_n<N>(dc_store_n<N>(o, lo), hi);
+}
+template <int N>
+__device__ __forceinline__ float* dc_row1_n(const float* v, int lane, float* o) {
+  float w[N], r[N];
+  dc_load_n<N>(v, lane, w);
+  row1_bcast_n<N>(w, r);
+  return dc_store_n<N>(o, r);
+}
+template <int N>
+__device__ __forceinline__ float* dc_oddrows_n(const float* v, int lane, float* o) {
+  float w[N];
+  dc_load_n<N>(v, lane, w);
+  oddrows_sum_n<N>(w);
+  return dc_store_n<N>(o, w);
+}
+DC_KERNEL dc_lanes_n(const float* in, float* out) {
+  const int lane = threadIdx.x;
+  const float* v = in + (size_t)blockIdx.x * DC_LANEN_VALS * 64;
+  float* o = out + (size_t)blockIdx.x * DC_LANEN_OUTS * 64 + lane;
+  o = dc_rowsum4_n<1>(v, lane, o);
+  o = dc_rowsum4_n<2>(v, lane, o);
+  o = dc_rowsum4_n<6>(v, lane, o);
+  o = dc_rowsum4_n<15>(v, lane, o);
+  o = dc_pairsum_n<1>(v, lane, o);
+  o = dc_pairsum_n<2>(v, lane, o);
+  o = dc_pairsum_n<27>(v, lane, o);
+  o = dc_row1_n<1>(v, lane, o);
+  o = dc_row1_n<2>(v, lane, o);
+  o = dc_row1_n<27>(v, lane, o);
+  o = dc_oddrows_n<1>(v, lane, o);
+  o = dc_oddrows_n<2>(v, lane, o);
+  o = dc_oddrows_n<21>(v, lane, o);
+  static_assert((1 + 2 + 6 + 15) + 2 * (1 + 2 + 27) + (1 + 2 + 27) + (1 + 2 + 21) == DC_LANEN_OUTS, "the list above");
+}
+extern "C" int go1dc_lanes_n(const float* in, float* out, int nsets, void* stream) {
+  if (nsets <= 0) return 0;
+  hipLaunchKernelGGL(dc_lanes_n, dim3(nsets), dim3(64), 0, (hipStream_t)stream, in, out);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // ---------------------------------------------------------------- segment geometry (contract on in go1_selfcol.h)
 // P0, P1, Q0, Q1: (n, 3); st: (n, 2)
 DC_KERNEL dc_seg_closest(const float* P0, const float* P1, const float* Q0, const float* Q1, float* st, int n) {

@@ -75,88 +75,126 @@ __device__ __forceinline__ float rowsum4(float p) {
   return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
 
-// N independent row sums stage by stage (all permlane16 swaps, then their adds, then the
-// permlane32 stage): one value at a time, every sum paid a register copy, a hazard nop and
-// the full swap latency, twice
+// ---------------------------------------------------------------- role sums, two values per swap
+// By 16-lane row, v_permlane16_swap(x, y) returns ([x0 y0 x2 y2], [x1 y1 x3 y3]) and v_permlane32_swap(x, y)
+// returns ([x0 x1 y0 y1], [x2 x3 y2 y3]).  Called as swap(v, v) an exchange moves one value, wastes half of what it
+// carries and costs a register copy (the instruction overwrites both operands).  The _n helpers below therefore
+// take their N values two at a time, (x, y) = (v[2 j], v[2 j + 1]); an odd last value takes the (v, v) form.  They
+// stay batched stage by stage (all swaps of a stage, then its adds), so no swap's latency or hazard nop is exposed.
+// On every lane whose result is read, each addition has the operands, in the order, of the one-value forms:
+// (r0 + r1) + (r2 + r3), or r1 + r3 with no zero added -- the bits are the same, signs of zero included.  Lanes of
+// rows that hold the other member's partial sums compute sums nobody reads.
+struct LanePair { float a, b; };
+__device__ __forceinline__ LanePair swap16(float x, float y) {
+  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
+  return {__uint_as_float(r[0]), __uint_as_float(r[1])};
+}
+__device__ __forceinline__ LanePair swap32(float x, float y) {
+  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
+  return {__uint_as_float(r[0]), __uint_as_float(r[1])};
+}
+
+// N independent row sums (r0 + r1) + (r2 + r3) on every lane.  Per pair: s = sum(swap16(x, y)) holds by row
+// [x0 + x1, y0 + y1, x2 + x3, y2 + y3]; t = sum(swap32(s, s)) holds [X, Y, X, Y]; swap16(t, t) returns (X, Y) on
+// every row.  3 swaps and 2 adds per pair where two values alone cost 4 and 4.
 template <int N>
 __device__ __forceinline__ void rowsum4_n(float* v) {
-  float a[N], b[N];
+  constexpr int P = N / 2, M = P + (N & 1);  // pairs; pairs and the odd tail
+  float s[M], t[M];
+  LanePair r[M];
 #pragma unroll
-  for (int i = 0; i < N; ++i) {
-    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i]), false, false);
-    a[i] = __uint_as_float(r[0]);
-    b[i] = __uint_as_float(r[1]);
+  for (int j = 0; j < P; ++j) r[j] = swap16(v[2 * j], v[2 * j + 1]);
+  if (N & 1) r[P] = swap16(v[N - 1], v[N - 1]);
+#pragma unroll
+  for (int j = 0; j < M; ++j) s[j] = r[j].a + r[j].b;
+#pragma unroll
+  for (int j = 0; j < M; ++j) r[j] = swap32(s[j], s[j]);
+#pragma unroll
+  for (int j = 0; j < M; ++j) t[j] = r[j].a + r[j].b;
+#pragma unroll
+  for (int j = 0; j < P; ++j) {
+    const LanePair o = swap16(t[j], t[j]);
+    v[2 * j] = o.a;
+    v[2 * j + 1] = o.b;
   }
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = a[i] + b[i];
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[i]), __float_as_uint(v[i]), false, false);
-    a[i] = __uint_as_float(r[0]);
-    b[i] = __uint_as_float(r[1]);
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = a[i] + b[i];
+  if (N & 1) v[N - 1] = t[P];
 }
 
-// N values that two bodies split between the row pairs (body L on rows 0-1, body H on rows 2-3):
-// the permlane16 stage sums each pair, then one permlane32 swap hands every lane both results --
-// its two outputs are the low-half value (rows 0-1) and the high-half value (rows 2-3) on every
-// lane.  Three VALU per value where two full row sums cost eight.
+// N values that two bodies split between the row pairs (body L on rows 0-1, body H on rows 2-3): lo = r0 + r1 and
+// hi = r2 + r3 on every lane.  Per pair: s = sum(swap16(x, y)) as above; (p, q) = swap32(s, s) are its rows
+// [s0 s1 s0 s1] and [s2 s3 s2 s3]; swap16(p, p) returns (lo_x, lo_y) and swap16(q, q) (hi_x, hi_y) on every row.
+// 4 swaps and 1 add per pair (4 and 2 for two values alone).
 template <int N>
 __device__ __forceinline__ void pairsum_rows_n(const float* v, float* lo, float* hi) {
-  float a[N], b[N], s[N];
+  constexpr int P = N / 2, M = P + (N & 1);
+  float s[M];
+  LanePair r[M];
 #pragma unroll
-  for (int i = 0; i < N; ++i) {
-    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i]), false, false);
-    a[i] = __uint_as_float(r[0]);
-    b[i] = __uint_as_float(r[1]);
+  for (int j = 0; j < P; ++j) r[j] = swap16(v[2 * j], v[2 * j + 1]);
+  if (N & 1) r[P] = swap16(v[N - 1], v[N - 1]);
+#pragma unroll
+  for (int j = 0; j < M; ++j) s[j] = r[j].a + r[j].b;
+#pragma unroll
+  for (int j = 0; j < M; ++j) r[j] = swap32(s[j], s[j]);
+#pragma unroll
+  for (int j = 0; j < P; ++j) {
+    const LanePair l = swap16(r[j].a, r[j].a);
+    lo[2 * j] = l.a;
+    lo[2 * j + 1] = l.b;
   }
 #pragma unroll
-  for (int i = 0; i < N; ++i) s[i] = a[i] + b[i];
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(s[i]), __float_as_uint(s[i]), false, false);
-    lo[i] = __uint_as_float(r[0]);
-    hi[i] = __uint_as_float(r[1]);
+  for (int j = 0; j < P; ++j) {
+    const LanePair h = swap16(r[j].b, r[j].b);
+    hi[2 * j] = h.a;
+    hi[2 * j + 1] = h.b;
   }
+  if (N & 1) { lo[N - 1] = r[P].a; hi[N - 1] = r[P].b; }
 }
 
-// Role "sums" of values that only some rows hold.  v_permlane16_swap(v, v) returns (rows 0 0 2 2, rows 1 1 3 3) of
-// v: its second output already carries the odd rows, so these take no select to zero the other rows and no add of
-// those zeros (x + 0 = x; only a -0 keeps its sign here, where 0 + -0 gave +0).
-// N values of row 1 onto every lane: one v_permlane32_swap spreads the second output's rows 0-1.
+// Role "sums" of values that only some rows hold: no select zeroes the other rows and no zero is added (x + 0 = x;
+// only a -0 keeps its sign here, where 0 + -0 gave +0).  What the other rows hold never reaches a result.
+// N values of row 1 onto every lane.  Per pair: p = swap32(x, y)[0] = [x0 x1 y0 y1]; r = swap16(p, p)[1] =
+// [x1 x1 y1 y1]; swap32(r, r) returns (x1, y1) on every row.  3 swaps per pair (4 for two values alone).
 template <int N>
 __device__ __forceinline__ void row1_bcast_n(const float* v, float* out) {
-  float b[N];
+  constexpr int P = N / 2, M = P + (N & 1);
+  float p[M];
 #pragma unroll
-  for (int i = 0; i < N; ++i) {
-    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i]), false, false);
-    b[i] = __uint_as_float(r[1]);
-  }
+  for (int j = 0; j < P; ++j) p[j] = swap32(v[2 * j], v[2 * j + 1]).a;
+  if (N & 1) p[P] = v[N - 1];  // (the one-value form: rows 1 1 3 3 of v, then its rows 0-1)
 #pragma unroll
-  for (int i = 0; i < N; ++i) {
-    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(b[i]), __float_as_uint(b[i]), false, false);
-    out[i] = __uint_as_float(r[0]);
+  for (int j = 0; j < M; ++j) p[j] = swap16(p[j], p[j]).b;
+#pragma unroll
+  for (int j = 0; j < P; ++j) {
+    const LanePair o = swap32(p[j], p[j]);
+    out[2 * j] = o.a;
+    out[2 * j + 1] = o.b;
   }
+  if (N & 1) out[N - 1] = swap32(p[P], p[P]).a;
 }
-// N sums row 1 + row 3 on every lane (rowsum4_n's order with rows 0 and 2 zero)
+// N sums row 1 + row 3 on every lane (rowsum4_n's order with rows 0 and 2 absent).  Per pair: s = sum(swap32(x, y))
+// holds x1 + x3 on row 1 and y1 + y3 on row 3; r = swap16(s, s)[1] = [s1 s1 s3 s3]; swap32(r, r) returns the two
+// sums on every row.  3 swaps and 1 add per pair (4 and 2 for two values alone).
 template <int N>
 __device__ __forceinline__ void oddrows_sum_n(float* v) {
-  float a[N], b[N];
+  constexpr int P = N / 2, M = P + (N & 1);
+  float s[M];
+  LanePair r[M];
 #pragma unroll
-  for (int i = 0; i < N; ++i) {
-    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i]), false, false);
-    b[i] = __uint_as_float(r[1]);
+  for (int j = 0; j < P; ++j) r[j] = swap32(v[2 * j], v[2 * j + 1]);
+#pragma unroll
+  for (int j = 0; j < P; ++j) s[j] = r[j].a + r[j].b;
+  if (N & 1) s[P] = v[N - 1];  // (the one-value form: rows 1 1 3 3 of v, then row 1 + row 3)
+#pragma unroll
+  for (int j = 0; j < M; ++j) s[j] = swap16(s[j], s[j]).b;
+#pragma unroll
+  for (int j = 0; j < M; ++j) r[j] = swap32(s[j], s[j]);
+#pragma unroll
+  for (int j = 0; j < P; ++j) {
+    v[2 * j] = r[j].a;
+    v[2 * j + 1] = r[j].b;
   }
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(b[i]), __float_as_uint(b[i]), false, false);
-    a[i] = __uint_as_float(r[0]);
-    b[i] = __uint_as_float(r[1]);
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = a[i] + b[i];
+  if (N & 1) v[N - 1] = r[P].a + r[P].b;
 }
 
 // min / max / or over the quad and the value of lane ^ D within it (DPP quad_perm)
