@@ -5,15 +5,15 @@
 
 #include "policy_tiles.h"
 
-#define PSTAMP(k)  // the per-phase stamps are a diagnostic of the full kernels (rollout.hip)
+#define PSTAMP(k)  // the per-phase stamps are a diagnostic of the full kernels (policy_full.h, policy_split.h)
 
 namespace {
 
 // policy_kernel without the critic (GO1_POLICY_STUDENT), and with TEACHER also without the adaptation module, whose
 // place in the actor's input the privileged observations take (GO1_POLICY_TEACHER).  A kernel of its own, in a source file of its
-// own, so that policy_kernel's code is what it was without the modes (in one file with it, these kernels changed
-// its register allocation).  The actor's tiles per wave, K order and partial-sum order
-// are policy_kernel's, so STUDENT writes the same bits.
+// own, so that policy_kernel's code is what it was without the modes (in one translation unit with it, these kernels
+// changed its register allocation; policy_kernel is in policy_full.h, a part of rollout.hip).  The actor's tiles per
+// wave, K order and partial-sum order are policy_kernel's, so STUDENT writes the same bits.
 template <bool TEACHER>
 __global__ __launch_bounds__(64 * PW) void policy_kernel_actor(go1_policy_args P) {
   __shared__ Act<PIN> xa;   // actor inputs (the adaptation module reads them first)

@@ -230,7 +230,8 @@ __device__ void dense_f32(const float* __restrict__ W, const float* __restrict__
 
 // policy_fallback's actor for the kernels of GO1_POLICY_STUDENT / TEACHER.  TEACHER: no adaptation module, the
 // actor's latent inputs (and `latent`) are the privileged observations.  A function of its own: policy_fallback stays
-// in rollout.hip with the GO1_POLICY_FULL kernels, whose code the modes leave as it was.
+// in policy_full.h (rollout.hip's translation unit) with the GO1_POLICY_FULL kernels, whose code the modes leave as it
+// was.
 template <bool TEACHER>
 __device__ void policy_fallback_actor(const go1_policy_args& P, int e0, int ne, float* buf) {
   const go1_policy_layer* L = P.layers;

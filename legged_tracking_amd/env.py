@@ -6,8 +6,8 @@ Mirrors the reference's env API for the hot path:
   TrajectoryTrackingEnv  <- go1_gym/envs/go1/trajectory_tracking/__init__.py:11-55
   HistoryWrapper         <- go1_gym/envs/wrappers/history_wrapper.py:6-41
 
-Everything per-env runs in the fused HIP kernel (legged_tracking_amd/csrc/go1_step.hip)
-through the C ABI (include/go1_mi355x.h); this module keeps only what the
+Everything per-env runs in the fused HIP kernel (legged_tracking_amd/csrc/go1_traj_step.h, a part
+of go1_step.hip) through the C ABI (include/go1_mi355x.h); this module keeps only what the
 reference keeps on the host or as global state:
 
   * common_step_counter, the global gravity schedule (_randomize_gravity :645-660,

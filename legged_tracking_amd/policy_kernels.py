@@ -3,9 +3,10 @@ actor-critic modules, the record / GAE / normalise kernels (HipRolloutKernels) a
 evaluate.  All of it is the host side of include/go1_rollout.h (learn_abi's structures); nothing here has a CPU or
 torch fall-back for a missing kernel.
 
-The plain module's forward is one launch (FusedPolicy: go1_policy_forward, csrc/rollout.hip); the height-map encoder
-module's is two (FusedEncoderPolicy: go1_heightmap_encode, csrc/encoder.hip, writes policy_input, then the same
-go1_policy_forward runs the three heads on it).
+The plain module's forward is one launch (FusedPolicy: go1_policy_forward in csrc/rollout.hip, the kernels in
+csrc/policy_full.h, policy_split.h and policy_actor.hip); the height-map encoder module's is two (FusedEncoderPolicy:
+go1_heightmap_encode, csrc/encoder.hip, writes policy_input, then the same go1_policy_forward runs the three heads on
+it).
 """
 import ctypes as C
 
@@ -83,7 +84,7 @@ def _heads_supported(ac, h):
 # ----------------------------------------------------------------------------- fused policy forwards
 class FusedPolicy:
     """ActorCritic forward for the rollout (act + evaluate) in one HIP kernel
-    (csrc/rollout.hip policy_kernel).  Re-pack after every optimiser step."""
+    (csrc/policy_full.h policy_kernel).  Re-pack after every optimiser step."""
 
     def __init__(self, ac, variant=0):
         self.ac = ac

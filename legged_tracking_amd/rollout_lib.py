@@ -1,5 +1,6 @@
-"""The HIP rollout library (libgo1_rollout.so: csrc/rollout.hip, policy_actor.hip, encoder.hip; C ABI
-include/go1_rollout.h), loaded once.  The learner's leaf module: it imports learn_abi and native only."""
+"""The HIP rollout library (libgo1_rollout.so: csrc/rollout.hip with its parts rollout_record.h, policy_full.h,
+policy_split.h and rollout_colsum.h, policy_actor.hip, encoder.hip; C ABI include/go1_rollout.h), loaded once.  The
+learner's leaf module: it imports learn_abi and native only."""
 import os
 
 import torch

@@ -6,9 +6,9 @@ Mirrors, for scripts/train_velocity_tracking.py's configuration on a plane:
                              on go1_gym/envs/base/legged_robot_velocity_tracking.py (bare :N below)
   HistoryWrapper          <- go1_gym/envs/wrappers/history_wrapper.py:6-41 (legged_tracking_amd.env)
 
-Everything per env runs in libgo1_velocity.so (legged_tracking_amd/csrc/go1_velocity.hip) through the C
-ABI of include/go1_velocity.h; this module keeps what the reference keeps on the host or globally: the
-configuration, common_step_counter with the global gravity schedule (:719-723, _randomize_gravity
+Everything per env runs in libgo1_velocity.so (legged_tracking_amd/csrc/go1_velocity.hip: the host side, with the
+kernels in its parts go1_vel_step.h and go1_vel_curriculum.h) through the C ABI of include/go1_velocity.h; this
+module keeps what the reference keeps on the host or globally: the configuration, common_step_counter with the global gravity schedule (:719-723, _randomize_gravity
 :564-579), and the extras (lazy: "train/episode" means are built from the kernel's compact episode log
 when read).  No CPU fallback: without the HIP library or a GPU the constructor raises.
 

@@ -8,7 +8,8 @@ tools/stamps.py; GO1_ISA_MARKS: section markers for tools/isa_sections.py).  Var
 measured and rejected are deleted from the source, not kept behind switches.  A front-end pass
 (hipcc -fsyntax-only, host and gfx950 device) per variant keeps them from rotting.  go1_velocity.hip
 has the curriculum launch's stamps (GO1_VEL_STAMPS, tools/vel_stamps.py); rollout.hip and ppo_update.hip keep their
-stamp builds only (GO1_POLICY_STAMPS, tools/policy_stamps.py; PPO_STAMPS, tools/xw_stamps.py)."""
+stamp builds only (GO1_POLICY_STAMPS, tools/policy_stamps.py; PPO_STAMPS, tools/xw_stamps.py).  The sources hold the
+host code and include their kernels as part headers, so every scan here is over a source's include closure."""
 import os
 import re
 import shutil
@@ -26,6 +27,8 @@ SRC = os.path.join(CSRC, "go1_step.hip")
 SCANNED = [f for f in B.include_closure([SRC]) if os.path.dirname(f) == CSRC]
 VEL_SRC = os.path.join(CSRC, "go1_velocity.hip")
 ROLLOUT_SRC = os.path.join(CSRC, "rollout.hip")
+# the sources of libgo1_rollout.so (rollout.hip, policy_actor.hip, encoder.hip)
+ROLLOUT_SRCS = [os.path.join(CSRC, s) for s in B.LIBS["libgo1_rollout.so"][0]]
 PPO_SRC = os.path.join(CSRC, "ppo_update.hip")
 INC = os.path.join(ROOT, "include")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -37,19 +40,29 @@ def _switches():
 
 
 def test_only_diagnostic_switches_remain():
-    src = "".join(open(f).read() for f in SCANNED + [VEL_SRC])
+    # go1_velocity.hip with every csrc header it reaches (its parts go1_vel_step.h and go1_vel_curriculum.h among them)
+    vel = [f for f in B.include_closure([VEL_SRC]) if os.path.dirname(f) == CSRC]
+    assert {os.path.join(CSRC, "go1_vel_step.h"), os.path.join(CSRC, "go1_vel_curriculum.h")} <= set(vel), vel
+    src = "".join(open(f).read() for f in SCANNED + [f for f in vel if f not in SCANNED])
     conds = set(re.findall(r"#\s*(?:if|ifdef|ifndef|elif)\s+(?:defined\()?(\w+)", src))
-    allowed = {"GO1_STAMPS", "GO1_ISA_MARKS", "GO1_VEL_STAMPS", "GO1_DEVICE_H"}
+    # the diagnostic switches, and the guards of the part headers (go1_device.h's, go1_step.hip's, go1_velocity.hip's)
+    allowed = {"GO1_STAMPS", "GO1_ISA_MARKS", "GO1_VEL_STAMPS", "GO1_DEVICE_H", "GO1_STEP_HIP", "GO1_VELOCITY_HIP"}
     stray = {c for c in conds if c.startswith("GO1_") and c not in allowed and not c.startswith("GO1_ABL_")}
     assert not stray, f"variant switches outside the diagnostic set: {sorted(stray)}"
     # the learn libraries and their headers: the two stamp builds and the header guards, nothing else
     # (ppo_update.hip with every csrc header it reaches: a switch in one of its parts is a switch in the engine)
     ppo = [f for f in B.include_closure([PPO_SRC]) if os.path.dirname(f) == CSRC]
     assert len(ppo) > 1, ppo
-    learn = "".join(open(f).read() for f in [ROLLOUT_SRC, *ppo, os.path.join(INC, "go1_rollout.h"),
+    # the three sources of libgo1_rollout.so with every csrc header they reach (rollout.hip's parts among them)
+    rollout = [f for f in B.include_closure(ROLLOUT_SRCS) if os.path.dirname(f) == CSRC]
+    assert {os.path.join(CSRC, h) for h in ("rollout_record.h", "policy_full.h", "policy_split.h", "rollout_colsum.h",
+                                            "policy_tiles.h", "split_mfma.h")} <= set(rollout), rollout
+    learn = "".join(open(f).read() for f in [*rollout, *ppo, os.path.join(INC, "go1_rollout.h"),
                                              os.path.join(INC, "go1_ppo.h")])
     conds = set(re.findall(r"#\s*(?:if|ifdef|ifndef|elif)\s+!?\s*(?:defined\s*\(?\s*)?(\w+)", learn))
-    allowed = {"GO1_POLICY_STAMPS", "PPO_STAMPS", "GO1_ROLLOUT_H", "GO1_PPO_H"}
+    # the two stamp builds and header guards: the ABI headers', rollout.hip's parts', policy_tiles.h's, split_mfma.h's
+    allowed = {"GO1_POLICY_STAMPS", "PPO_STAMPS", "GO1_ROLLOUT_H", "GO1_PPO_H", "GO1_ROLLOUT_HIP", "GO1_POLICY_TILES_H",
+               "GO1_SPLIT_MFMA_H"}
     stray = {c for c in conds if c.startswith(("GO1_", "PPO_")) and c not in allowed}
     assert {"GO1_POLICY_STAMPS", "PPO_STAMPS"} <= conds and not stray, \
         f"variant switches in rollout.hip / ppo_update.hip: {sorted(stray)}"
@@ -80,7 +93,10 @@ def test_devcheck_library_is_built_as_the_step_kernels_are_and_loads():
     srcs, flags = B.LIBS[D.NAME]
     assert srcs == ["go1_devcheck.hip"] and flags == B.STEP_FLAGS
     assert os.path.join(CSRC, "go1_device.h") in B.lib_files(D.NAME)
-    step_parts = {f for f in SCANNED if f.endswith(".h") and os.path.basename(f) != "go1_step_shared.h"}
+    # the device layer: every header go1_step.hip reaches but the scaffold and the source's own kernel parts
+    own = ("go1_step_shared.h", "go1_traj_step.h", "go1_traj_aux.h")
+    step_parts = {f for f in SCANNED if f.endswith(".h") and os.path.basename(f) not in own}
+    assert step_parts == {f for f in B.include_closure([os.path.join(CSRC, "go1_device.h")]) if os.path.dirname(f) == CSRC}
     assert step_parts <= set(B.lib_files(D.NAME))
     lib = D.lib()
     for fn in ("go1dc_pm1", "go1dc_pm2", "go1dc_softsign2", "go1dc_quat", "go1dc_solve6", "go1dc_lanes",

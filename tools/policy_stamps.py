@@ -1,6 +1,7 @@
-"""Phase timing of the policy kernel (diagnostic build with -DGO1_POLICY_STAMPS).
+"""Phase timing of the policy kernel (diagnostic build with -DGO1_POLICY_STAMPS; the PSTAMP phases are
+in csrc/policy_full.h and csrc/policy_split.h, parts of rollout.hip).
 
-  local:  hipcc ... -DGO1_POLICY_STAMPS -o legged_tracking_amd/_build/libgo1_rollout_stamps.so rollout.hip
+  local:  hipcc ... -DGO1_POLICY_STAMPS -o legged_tracking_amd/_build/libgo1_rollout_stamps.so rollout.hip policy_actor.hip encoder.hip
   gpurun: python tools/policy_stamps.py [--variant 1]   (default: variant 0, policy_kernel_split)
 
 Phases end at the kernel's barriers: 1 input staging, 2 adaptation L1, 3 adaptation L2,
@@ -48,7 +49,7 @@ def main():
     t_full = buf.reshape(512, 16, 12).astype(np.int64)[:256]
     t_all = t_full[:, :, :9]
     used = t_all[:, 0, 0] != 0  # workgroups of the launch (the stamp buffer holds 256)
-    na = -(-n // (16 * 2))  # actor workgroups: SPLIT_ET_A = 2 env tiles each (rollout.hip)
+    na = -(-n // (16 * 2))  # actor workgroups: SPLIT_ET_A = 2 env tiles each (policy_split.h)
     groups = [("all", t_all[used])] if variant else [("actor workgroups", t_all[:na][used[:na]]),
                                                      ("critic workgroups", t_all[na:][used[na:]])]
     for label, t in groups:

@@ -1,4 +1,5 @@
-"""Section timing of the velocity curriculum launch's block 0 (diagnostic build with -DGO1_VEL_STAMPS).
+"""Section timing of the velocity curriculum launch's block 0 (diagnostic build with -DGO1_VEL_STAMPS;
+the VSTAMP sections are in csrc/go1_vel_curriculum.h, a part of go1_velocity.hip).
 
   local:  hipcc --offload-arch=gfx950 -O3 -fPIC -shared -std=c++17 -ffp-contract=off -fno-slp-vectorize \\
               -mllvm -amdgpu-kernarg-preload-count=16 -DGO1_VEL_STAMPS -o legged_tracking_amd/_build/libgo1_velocity_stamps.so \\
