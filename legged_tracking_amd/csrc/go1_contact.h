@@ -238,128 +238,215 @@ __device__ __forceinline__ void verts_fetch(const Terr& T, const int* vi, const 
       if ((out >> n) & 1u) h[n] = f2{tile_at(T, 1, vi[n], vj[n]), tile_at(T, 0, vi[n], vj[n])};
   }
 }
-// deepest point of one segment (world ends A, B): t and SEG_CELL.  Two batches of candidates (the ends and the lines
-// u = k; the lines v = k and the diagonals), each gathering its mesh vertices (verts_fetch) before comparing them
-__device__ __forceinline__ float seg_deepest(const Terr& T, const float* A, const float* B, float r, int& cell) {
-  if (!T.tile) {  // the plane: the lower end
-    cell = SEG_CELL(0, 0, false);
-    return seg_quant(r - B[2]) > seg_quant(r - A[2]) ? 1.0f : 0.0f;
+// the plane: the lower end (ties: A)
+__device__ __forceinline__ float seg_plane(const float* A, const float* B, float r, int& cell) {
+  cell = SEG_CELL(0, 0, false);
+  return seg_quant(r - B[2]) > seg_quant(r - A[2]) ? 1.0f : 0.0f;
+}
+// deepest point of one segment (world ends A, B): t and SEG_CELL.  The candidates, offered in this order (seg_offer
+// keeps the first of equal keys): end A, end B, NU lines u = k, NV lines v = k, ND diagonals.  <3, 3, 4> holds every
+// crossing of a half link (above); <1, 1, 2> those of a segment shorter than one cell (SEG_SHORT_MAX).  Two batches
+// of candidates (the ends and the lines u = k; the lines v = k and the diagonals), each gathering its mesh vertices
+// (verts_fetch) before comparing them -- or, ONE_BATCH, all 6 + 2 (NU + NV + ND) vertices in one gather with one wait
+struct SegLine {  // the segment in cell units, its first end's cell
+  float uA, vA, uB, vB, du, dv, dw, dz, zA, zB, r;
+  int iA, jA;
+};
+// the first batch's candidates -- the ends (vertices c00, c11 and c01 on the upper triangle / c10) and the grid lines
+// u = k (the edge (k, j) - (k, j + 1), entered from cell k - 1 (du > 0) or k) -- and their 6 + 2 NU vertices
+template <int NU>
+struct SegFirst {
+  float ca[2 + NU], cb[2], ct[NU];
+  int ccell[2 + NU];
+  bool cup[2], cval[NU];
+};
+template <int NU>
+__device__ __forceinline__ void seg_first(const SegLine& L, SegFirst<NU>& c, int* vi, int* vj) {
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const float u = e ? L.uB : L.uA, v = e ? L.vB : L.vA;
+    const float fu = floorf(u), fv = floorf(v);
+    const int i = (int)fu, j = (int)fv;
+    c.ca[e] = u - fu;
+    c.cb[e] = v - fv;
+    c.cup[e] = c.ca[e] < c.cb[e];
+    c.ccell[e] = SEG_CELL(i, j, c.cup[e]);
+    vi[3 * e] = i; vj[3 * e] = j;
+    vi[3 * e + 1] = i + 1; vj[3 * e + 1] = j + 1;
+    vi[3 * e + 2] = c.cup[e] ? i : i + 1; vj[3 * e + 2] = c.cup[e] ? j + 1 : j;
   }
+  const int k0 = (int)floorf(fminf(L.uA, L.uB)) + 1;
+  const float hi = fmaxf(L.uA, L.uB), rdu = L.du != 0.0f ? frcp(L.du) : 0.0f;
+#pragma unroll
+  for (int m = 0; m < NU; ++m) {
+    const int k = k0 + m, n = 6 + 2 * m;
+    const bool valid = (float)k < hi;
+    const float t = valid ? ((float)k - L.uA) * rdu : 0.0f, v = L.vA + L.dv * t, fv = floorf(v), b = v - fv;
+    const int j = (int)fv, i = L.du > 0.0f ? k - 1 : k;
+    c.ct[m] = t; c.ca[2 + m] = b; c.cval[m] = valid;
+    c.ccell[2 + m] = SEG_CELL(i, j, (float)(k - i) < b);
+    // an invalid candidate (beyond the segment's crossings) reads A's cell instead of an edge up to 4 cells off,
+    // which could leave the LDS patch
+    vi[n] = valid ? k : L.iA; vj[n] = valid ? j : L.jA;
+    vi[n + 1] = vi[n]; vj[n + 1] = vj[n] + 1;
+  }
+}
+template <int NU>
+__device__ __forceinline__ void seg_first_offer(const SegLine& L, const SegFirst<NU>& c, const f2* h, SegBest& sb) {
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const f2 c00 = h[3 * e], c11 = h[3 * e + 1], cx = h[3 * e + 2];
+    const f2 da = c.cup[e] ? c11 - cx : cx - c00, db = c.cup[e] ? cx - c00 : c11 - cx;
+    seg_offer(sb, c00 + c.ca[e] * da + c.cb[e] * db, e ? L.zB : L.zA, L.r, (float)e, c.ccell[e], true);
+  }
+#pragma unroll
+  for (int m = 0; m < NU; ++m) {
+    const f2 p0 = h[6 + 2 * m], p1 = h[7 + 2 * m];
+    seg_offer(sb, p0 + c.ca[2 + m] * (p1 - p0), L.zA + L.dz * c.ct[m], L.r, c.ct[m], c.ccell[2 + m], c.cval[m]);
+  }
+}
+// the second batch's -- the grid lines v = k (the edge (i, k) - (i + 1, k), entered from cell k - 1 (dv > 0) or k)
+// and the cell diagonals u - v = k (the point (i + a, j + a) of cell (i, j), i - j = k, entered from the upper
+// triangle (dw > 0: u - v grows through k, a < b before) or the lower) -- and their 2 (NV + ND) vertices
+template <int NL>
+struct SegSecond {
+  float ca[NL], ct[NL];
+  int ccell[NL];
+  bool cval[NL];
+};
+template <int NV, int ND>
+__device__ __forceinline__ void seg_second(const SegLine& L, SegSecond<NV + ND>& c, int* vi, int* vj) {
+  {
+    const int k0 = (int)floorf(fminf(L.vA, L.vB)) + 1;
+    const float hi = fmaxf(L.vA, L.vB), rdv = L.dv != 0.0f ? frcp(L.dv) : 0.0f;
+#pragma unroll
+    for (int m = 0; m < NV; ++m) {
+      const int k = k0 + m, n = 2 * m;
+      const bool valid = (float)k < hi;
+      const float t = valid ? ((float)k - L.vA) * rdv : 0.0f, u = L.uA + L.du * t, fu = floorf(u), a = u - fu;
+      const int i = (int)fu, j = L.dv > 0.0f ? k - 1 : k;
+      c.ct[m] = t; c.ca[m] = a; c.cval[m] = valid;
+      c.ccell[m] = SEG_CELL(i, j, a < (float)(k - j));
+      vi[n] = valid ? i : L.iA; vj[n] = valid ? k : L.jA;
+      vi[n + 1] = vi[n] + 1; vj[n + 1] = vj[n];
+    }
+  }
+  {
+    const float wA = L.uA - L.vA, wB = L.uB - L.vB;
+    const int k0 = (int)floorf(fminf(wA, wB)) + 1;
+    const float hi = fmaxf(wA, wB), rdw = L.dw != 0.0f ? frcp(L.dw) : 0.0f;
+#pragma unroll
+    for (int m = 0; m < ND; ++m) {
+      const int k = k0 + m, cc = NV + m, n = 2 * cc;
+      const bool valid = (float)k < hi;
+      const float t = valid ? ((float)k - wA) * rdw : 0.0f, u = L.uA + L.du * t, fu = floorf(u), a = u - fu;
+      const int i = (int)fu, j = i - k;
+      c.ct[cc] = t; c.ca[cc] = a; c.cval[cc] = valid;
+      c.ccell[cc] = SEG_CELL(i, j, L.dw > 0.0f);
+      vi[n] = valid ? i : L.iA; vj[n] = valid ? j : L.jA;
+      vi[n + 1] = vi[n] + 1; vj[n + 1] = vj[n] + 1;
+    }
+  }
+}
+template <int NL>
+__device__ __forceinline__ void seg_second_offer(const SegLine& L, const SegSecond<NL>& c, const f2* h, SegBest& sb) {
+#pragma unroll
+  for (int k = 0; k < NL; ++k) {
+    const f2 p0 = h[2 * k], p1 = h[2 * k + 1];
+    seg_offer(sb, p0 + c.ca[k] * (p1 - p0), L.zA + L.dz * c.ct[k], L.r, c.ct[k], c.ccell[k], c.cval[k]);
+  }
+}
+template <int NU = 3, int NV = 3, int ND = 4, bool ONE_BATCH = false>
+__device__ __forceinline__ float seg_deepest(const Terr& T, const float* A, const float* B, float r, int& cell) {
+  if (!T.tile) return seg_plane(A, B, r, cell);
+  constexpr int N1 = 6 + 2 * NU, N2 = 2 * (NV + ND);
   const float ihs = frcp(T.hs);
-  const float uA = fminf(fmaxf(A[0] * ihs, -4.0f), (float)(T.nx + 4)), vA = fminf(fmaxf(A[1] * ihs, -4.0f), (float)(T.ny + 4));
-  const float uB = fminf(fmaxf(B[0] * ihs, -4.0f), (float)(T.nx + 4)), vB = fminf(fmaxf(B[1] * ihs, -4.0f), (float)(T.ny + 4));
-  const float du = uB - uA, dv = vB - vA, dw = du - dv, dz = B[2] - A[2], zA = A[2];
-  // an invalid candidate (beyond the segment's crossings) reads A's cell instead of an edge up to 4 cells off, which
-  // could leave the LDS patch
-  const int iA = (int)floorf(uA), jA = (int)floorf(vA);
+  SegLine L;
+  L.uA = fminf(fmaxf(A[0] * ihs, -4.0f), (float)(T.nx + 4)); L.vA = fminf(fmaxf(A[1] * ihs, -4.0f), (float)(T.ny + 4));
+  L.uB = fminf(fmaxf(B[0] * ihs, -4.0f), (float)(T.nx + 4)); L.vB = fminf(fmaxf(B[1] * ihs, -4.0f), (float)(T.ny + 4));
+  L.du = L.uB - L.uA; L.dv = L.vB - L.vA; L.dw = L.du - L.dv; L.dz = B[2] - A[2]; L.zA = A[2]; L.zB = B[2];
+  L.r = r;
+  L.iA = (int)floorf(L.uA); L.jA = (int)floorf(L.vA);
   SegBest sb;
   sb.key = -2147483647 - 1;
   sb.t = 0.0f;
   sb.cell = SEG_CELL(0, 0, false);
-  {  // the ends (vertices c00, c11 and c01 on the upper triangle / c10) and the grid lines u = k (the edge (k, j) -
-     // (k, j + 1), entered from cell k - 1 (du > 0) or k)
-    int vi[12], vj[12];
-    float ca[5], cb[2], ct[3];
-    int ccell[5];
-    bool cup[2], cval[3];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const float u = e ? uB : uA, v = e ? vB : vA;
-      const float fu = floorf(u), fv = floorf(v);
-      const int i = (int)fu, j = (int)fv;
-      ca[e] = u - fu;
-      cb[e] = v - fv;
-      cup[e] = ca[e] < cb[e];
-      ccell[e] = SEG_CELL(i, j, cup[e]);
-      vi[3 * e] = i; vj[3 * e] = j;
-      vi[3 * e + 1] = i + 1; vj[3 * e + 1] = j + 1;
-      vi[3 * e + 2] = cup[e] ? i : i + 1; vj[3 * e + 2] = cup[e] ? j + 1 : j;
-    }
-    const int k0 = (int)floorf(fminf(uA, uB)) + 1;
-    const float hi = fmaxf(uA, uB), rdu = du != 0.0f ? frcp(du) : 0.0f;
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      const int k = k0 + m, n = 6 + 2 * m;
-      const bool valid = (float)k < hi;
-      const float t = valid ? ((float)k - uA) * rdu : 0.0f, v = vA + dv * t, fv = floorf(v), b = v - fv;
-      const int j = (int)fv, i = du > 0.0f ? k - 1 : k;
-      ct[m] = t; ca[2 + m] = b; cval[m] = valid;
-      ccell[2 + m] = SEG_CELL(i, j, (float)(k - i) < b);
-      vi[n] = valid ? k : iA; vj[n] = valid ? j : jA;
-      vi[n + 1] = vi[n]; vj[n + 1] = vj[n] + 1;
-    }
-    f2 h[12];
-    verts_fetch<12>(T, vi, vj, h);
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const f2 c00 = h[3 * e], c11 = h[3 * e + 1], cx = h[3 * e + 2];
-      const f2 da = cup[e] ? c11 - cx : cx - c00, db = cup[e] ? cx - c00 : c11 - cx;
-      seg_offer(sb, c00 + ca[e] * da + cb[e] * db, e ? B[2] : zA, r, (float)e, ccell[e], true);
-    }
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      const f2 p0 = h[6 + 2 * m], p1 = h[7 + 2 * m];
-      seg_offer(sb, p0 + ca[2 + m] * (p1 - p0), zA + dz * ct[m], r, ct[m], ccell[2 + m], cval[m]);
-    }
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  {  // the grid lines v = k (the edge (i, k) - (i + 1, k), entered from cell k - 1 (dv > 0) or k) and the cell
-     // diagonals u - v = k (the point (i + a, j + a) of cell (i, j), i - j = k, entered from the upper triangle (dw > 0:
-     // u - v grows through k, a < b before) or the lower)
-    int vi[14], vj[14];
-    float ca[7], ct[7];
-    int ccell[7];
-    bool cval[7];
+  if constexpr (ONE_BATCH) {
+    int vi[N1 + N2], vj[N1 + N2];
+    SegFirst<NU> c1;
+    SegSecond<NV + ND> c2;
+    seg_first<NU>(L, c1, vi, vj);
+    seg_second<NV, ND>(L, c2, vi + N1, vj + N1);
+    f2 h[N1 + N2];
+    verts_fetch<N1 + N2>(T, vi, vj, h);
+    seg_first_offer<NU>(L, c1, h, sb);
+    seg_second_offer<NV + ND>(L, c2, h + N1, sb);
+  } else {
     {
-      const int k0 = (int)floorf(fminf(vA, vB)) + 1;
-      const float hi = fmaxf(vA, vB), rdv = dv != 0.0f ? frcp(dv) : 0.0f;
-#pragma unroll
-      for (int m = 0; m < 3; ++m) {
-        const int k = k0 + m, n = 2 * m;
-        const bool valid = (float)k < hi;
-        const float t = valid ? ((float)k - vA) * rdv : 0.0f, u = uA + du * t, fu = floorf(u), a = u - fu;
-        const int i = (int)fu, j = dv > 0.0f ? k - 1 : k;
-        ct[m] = t; ca[m] = a; cval[m] = valid;
-        ccell[m] = SEG_CELL(i, j, a < (float)(k - j));
-        vi[n] = valid ? i : iA; vj[n] = valid ? k : jA;
-        vi[n + 1] = vi[n] + 1; vj[n + 1] = vj[n];
-      }
+      int vi[N1], vj[N1];
+      SegFirst<NU> c;
+      seg_first<NU>(L, c, vi, vj);
+      f2 h[N1];
+      verts_fetch<N1>(T, vi, vj, h);
+      seg_first_offer<NU>(L, c, h, sb);
     }
+    __builtin_amdgcn_sched_barrier(0);
     {
-      const float wA = uA - vA, wB = uB - vB;
-      const int k0 = (int)floorf(fminf(wA, wB)) + 1;
-      const float hi = fmaxf(wA, wB), rdw = dw != 0.0f ? frcp(dw) : 0.0f;
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const int k = k0 + m, c = 3 + m, n = 2 * c;
-        const bool valid = (float)k < hi;
-        const float t = valid ? ((float)k - wA) * rdw : 0.0f, u = uA + du * t, fu = floorf(u), a = u - fu;
-        const int i = (int)fu, j = i - k;
-        ct[c] = t; ca[c] = a; cval[c] = valid;
-        ccell[c] = SEG_CELL(i, j, dw > 0.0f);
-        vi[n] = valid ? i : iA; vj[n] = valid ? j : jA;
-        vi[n + 1] = vi[n] + 1; vj[n + 1] = vj[n] + 1;
-      }
-    }
-    f2 h[14];
-    verts_fetch<14>(T, vi, vj, h);
-#pragma unroll
-    for (int c = 0; c < 7; ++c) {
-      const f2 p0 = h[2 * c], p1 = h[2 * c + 1];
-      seg_offer(sb, p0 + ca[c] * (p1 - p0), zA + dz * ct[c], r, ct[c], ccell[c], cval[c]);
+      int vi[N2], vj[N2];
+      SegSecond<NV + ND> c;
+      seg_second<NV, ND>(L, c, vi, vj);
+      f2 h[N2];
+      verts_fetch<N2>(T, vi, vj, h);
+      seg_second_offer<NV + ND>(L, c, h, sb);
     }
   }
   cell = sb.cell;
   return sb.t;
 }
-// the lane's two segments (x, y halves of the contact pass)
-__device__ __forceinline__ f2 seg_deepest2(const Terr& T, const f2* A, const f2* B, f2 r, int* cell) {
-  const float a0[3] = {A[0].x, A[1].x, A[2].x}, b0[3] = {B[0].x, B[1].x, B[2].x};
-  const float a1[3] = {A[0].y, A[1].y, A[2].y}, b1[3] = {B[0].y, B[1].y, B[2].y};
-  const float tx = seg_deepest(T, a0, b0, r.x, cell[0]);
+// The short pass's bound.  A segment of SEG_SHORT_MAX metres on cells of at least SEG_MIN_HS (go1_create refuses
+// finer grids) spans less than one cell, so it crosses at most 1 line u = k, 1 line v = k and, u - v moving by less
+// than sqrt 2 cells, 2 diagonals: seg_deepest<1, 1, 2> offers every crossing it has.  The hip capsule is the longest
+// such segment of the model (go1_create pins the model block bit for bit to go1_model_consts.h).
+#define SEG_MIN_HS 0.0499f
+#define SEG_SHORT_MAX (GO1_MODEL_F32[177] - GO1_MODEL_F32[176])  // hip_y1 - hip_y0
+static_assert(SEG_SHORT_MAX > 0.0f && SEG_SHORT_MAX / SEG_MIN_HS < 1.0f, "the hip capsule crosses at most 1 grid line");
+static_assert(SEG_SHORT_MAX / SEG_MIN_HS * 1.41421357f < 2.0f, "the hip capsule crosses at most 2 cell diagonals");
+// The lane's two segments (x, y halves of the contact pass; lane = 16 role + ...).  Of a leg's eight (role, half)
+// slots only four are half links, the length the full candidate set is for:
+//   role 0: thigh half | thigh half     role 1: hip capsule (SEG_SHORT_MAX) | trunk corner (a point)
+//   role 2: calf half  | calf half      role 3: foot (a point)              | trunk corner (a point)
+// so the halves change rows first: swap16(x, y) holds by row a = [x0 y0 x2 y2], the four half links, and b =
+// [x1 y1 x3 y3], the short segments.  One full pass over a and one short, single-batch pass over b then do the work
+// of two full passes, and swap16(a, b) takes (t, cell) home.  rs: the radii of (a, b) on this lane, which are the
+// model's by row and need no exchange.  Every candidate is computed on some lane exactly as before.
+// The short pass runs first: in the other order the README-config kernel needs 498 registers instead of 494 and the
+// generic kernels spill.
+// The plane has no candidates and stays in place with no exchange where the view is the plane at compile time (the
+// velocity kernel).  A run-time test here -- a branch around both passes -- cost the step kernels 45 to 75 spilled
+// registers; there a plane config takes the exchange and seg_deepest's own test, with the same result.
+__device__ __forceinline__ f2 seg_deepest2(const Terr& T, const f2* A, const f2* B, f2 r, f2 rs, int* cell) {
+  if (__builtin_constant_p(T.tile == nullptr) && !T.tile) {
+    const float a0[3] = {A[0].x, A[1].x, A[2].x}, b0[3] = {B[0].x, B[1].x, B[2].x};
+    const float a1[3] = {A[0].y, A[1].y, A[2].y}, b1[3] = {B[0].y, B[1].y, B[2].y};
+    const float tx = seg_plane(a0, b0, r.x, cell[0]), ty = seg_plane(a1, b1, r.y, cell[1]);
+    return f2{tx, ty};
+  }
+  LanePair sA[3], sB[3];  // all swaps first, then their uses
+#pragma unroll
+  for (int i = 0; i < 3; ++i) sA[i] = swap16(A[i].x, A[i].y);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) sB[i] = swap16(B[i].x, B[i].y);
+  const float a0[3] = {sA[0].a, sA[1].a, sA[2].a}, b0[3] = {sB[0].a, sB[1].a, sB[2].a};
+  const float a1[3] = {sA[0].b, sA[1].b, sA[2].b}, b1[3] = {sB[0].b, sB[1].b, sB[2].b};
+  int ca, cb;
+  const float tb = seg_deepest<1, 1, 2, true>(T, a1, b1, rs.y, cb);
   __builtin_amdgcn_sched_barrier(0);  // one segment's vertex batch live at a time
-  const float ty = seg_deepest(T, a1, b1, r.y, cell[1]);
-  return f2{tx, ty};
+  const float ta = seg_deepest<3, 3, 4, false>(T, a0, b0, rs.x, ca);
+  const LanePair t = swap16(ta, tb);
+  const auto c = __builtin_amdgcn_permlane16_swap((uint32_t)ca, (uint32_t)cb, false, false);
+  cell[0] = (int)c[0];
+  cell[1] = (int)c[1];
+  return f2{t.a, t.b};
 }
 
 // World position of this leg's foot body origin (rigid_body_state[:, feet, 0:3] after

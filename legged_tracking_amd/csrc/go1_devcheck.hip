@@ -335,3 +335,54 @@ extern "C" int go1dc_terrain(int mode, const float* tiles, const float* stage, c
                      B, r, hq, seg_t, seg_cell, hqc);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// ---------------------------------------------------------------- the lane's segment pair: one wave per "env"
+// The product's seg_deepest2 with the Terr set-up and modes of dc_terrain.  Lane l of env e passes its two segments
+// (x, y halves) as the sub-step does, its role being l / 16: the x halves of rows 0 and 2 and both halves of their y
+// take the full search, the others the short one (at most SEG_SHORT_MAX long).  A, B: (nenv * 64, 2, 3); r, seg_t:
+// (nenv * 64, 2); seg_cell: (nenv * 64, 2) ints.  The radii reach the search's row layout by the exchange the ends
+// take (the sub-step selects the model's there).
+DC_KERNEL dc_seg_pair(int mode, const float* tiles, const float* stage, const int* env_i, float hs, const float* A,
+                      const float* B, const float* r, float* seg_t, int* seg_cell) {
+  __shared__ float2 s_patch[PSZX * PSZY];
+  const int lane = threadIdx.x, e = blockIdx.x;
+  const int off = env_i[5 * e], nx = env_i[5 * e + 1], ny = env_i[5 * e + 2], pi0 = env_i[5 * e + 3],
+            pj0 = env_i[5 * e + 4];
+  const float* st = stage + off;
+  for (int c = lane; c < PSZX * PSZY; c += 64) {
+    const int gi = min(max(pi0 + c / PSZY, 0), nx - 1), gj = min(max(pj0 + c % PSZY, 0), ny - 1);
+    s_patch[c] = make_float2(st[((size_t)nx + gi) * ny + gj], st[(size_t)gi * ny + gj]);
+  }
+  __syncthreads();
+  Terr T;
+  T.tile = mode == 2 ? nullptr : tiles + off;
+  T.nx = nx;
+  T.ny = ny;
+  T.hs = hs;
+  T.patch = mode == 0 ? s_patch : nullptr;
+  T.pi0 = pi0;
+  T.pj0 = pj0;
+  const size_t i = (size_t)e * 64 + lane;
+  f2 a[3], b[3];
+  for (int k = 0; k < 3; ++k) {
+    a[k] = f2{A[6 * i + k], A[6 * i + 3 + k]};
+    b[k] = f2{B[6 * i + k], B[6 * i + 3 + k]};
+  }
+  const f2 rr = f2{r[2 * i], r[2 * i + 1]};
+  const LanePair rp = swap16(rr.x, rr.y);
+  int cell[2];
+  const f2 t = seg_deepest2(T, a, b, rr, f2{rp.a, rp.b}, cell);
+  seg_t[2 * i] = t.x;
+  seg_t[2 * i + 1] = t.y;
+  seg_cell[2 * i] = cell[0];
+  seg_cell[2 * i + 1] = cell[1];
+}
+extern "C" int go1dc_seg_pair(int mode, const float* tiles, const float* stage, const int* env_i, float hs, int nenv,
+                              const float* A, const float* B, const float* r, float* seg_t, int* seg_cell,
+                              void* stream) {
+  if (mode < 0 || mode > 2 || !(hs >= SEG_MIN_HS)) return -1;
+  if (nenv <= 0) return 0;
+  hipLaunchKernelGGL(dc_seg_pair, dim3(nenv), dim3(64), 0, (hipStream_t)stream, mode, tiles, stage, env_i, hs, A, B, r,
+                     seg_t, seg_cell);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}

@@ -69,6 +69,10 @@ struct Held {
 //   role 3: foot sphere, trunk corner 2 leg + 1                      (body: calf, trunk)
 // so each wave has four envs and the whole grid fills every SIMD.  The lane's self-collision primitive is its x
 // half's link (thigh, hip, calf, foot).
+// The capsule search alone runs in another layout (seg_deepest2): the x and y halves change rows (swap16), so that
+// rows 0-3 hold thigh upper, thigh lower, calf upper, calf lower in one half -- the four half links, searched with
+// the full candidate set -- and hip capsule, corner, foot, corner in the other, searched with the short one; t and
+// cell come home through the same exchange, and H.ts, cell[] hold the lane's own halves as everywhere else.
 // cf_raw: this lane's reported contact forces (x half with the own primitive's self-contact force, y half, the
 // trunk's self-collision reaction of the lane's box contact and, on one lane, the trunk faces').
 // K: sub_consts(cfg); H: the control step's held choices, written when face_scan_now and read otherwise.
@@ -313,7 +317,9 @@ __device__ __forceinline__ void phys_substep(CCfg* __restrict__ cfg, const PhysK
         cell[0] = SEG_CELL((int)floorf(wA[0].x / T.hs), (int)floorf(wA[1].x / T.hs), false);
         cell[1] = SEG_CELL((int)floorf(wA[0].y / T.hs), (int)floorf(wA[1].y / T.hs), false);
 #else
-        ts = seg_deepest2(T, wA, wB, rr, cell);
+        // (the radii in the search's row layout: the half links' by row pair; hip, corner, foot, corner)
+        const f2 rs = f2{(role & 2) ? calf_r : thigh_r, sel4(role, hip_r, 0.0f, foot_r, 0.0f)};
+        ts = seg_deepest2(T, wA, wB, rr, rs, cell);
 #endif
         H.ts = ts;
       } else {

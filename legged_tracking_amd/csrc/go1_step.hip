@@ -137,8 +137,9 @@ int go1_create(const go1_config* cfg, go1_handle** out) {
   if (cfg->decimation <= 0 || cfg->n_internal <= 0) return fail(GO1_E_ARG, "go1_create: decimation/n_internal");
   if (cfg->terrain_kind == 1 && (cfg->hf_nx < 2 || cfg->hf_ny < 2)) return fail(GO1_E_ARG, "go1_create: tile shape");
   // the capsules' deepest-point search (go1_contact.h seg_deepest) takes at most 3 grid lines per direction and 4 cell
-  // diagonals per half link (0.1065 m): cells of at least 0.05 m
-  if (cfg->terrain_kind == 1 && !(cfg->horizontal_scale >= 0.0499f))
+  // diagonals per half link (0.1065 m), and 1 line per direction and 2 diagonals for the hip capsule (0.04 m,
+  // SEG_SHORT_MAX; seg_deepest2's short pass): cells of at least 0.05 m
+  if (cfg->terrain_kind == 1 && !(cfg->horizontal_scale >= SEG_MIN_HS))
     return fail(GO1_E_ARG, "go1_create: horizontal_scale < 0.05 m is not supported by the capsule contact search");
   if (cfg->rand_interval <= 0) return fail(GO1_E_ARG, "go1_create: rand_interval");
   // a partial last wave exists in the streamed kernel only (any scan grid but 21 x 11)
