@@ -28,6 +28,9 @@ LIBS = {
     "libgo1_render.so": (["go1_render.hip"], []),
     # the episode tracer (trace.py): a library of its own, so the render and step ABIs and their size checks stay put
     "libgo1_trace.so": (["go1_trace.hip"], []),
+    # the local target planner (plan.py): one launch after the step kernel, built as the step kernels are because it
+    # shares their torch-order math (go1_torch_math.h) bit for bit; no file in common with the render / trace libraries
+    "libgo1_plan.so": (["go1_plan.hip"], STEP_FLAGS),
     # test-only: one thin kernel per device function of go1_device.h (tests/devcheck.py), built as the step kernels are
     "libgo1_devcheck.so": (["go1_devcheck.hip"], STEP_FLAGS),
 }

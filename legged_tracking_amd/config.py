@@ -183,7 +183,13 @@ def make_cfg():
             switch_dist = 0.05
             switch_yaw = 0.5
             sampling_based_planning = False
-            plan_interval = 10
+            plan_interval = 10  # replan every plan_interval steps
+            # (1575, 6) x y z roll pitch yaw in the robot frame (legged_robot_trajectory_tracking_config.py:167-175)
+            candidate_target_poses = np.stack(np.meshgrid(
+                np.linspace(0.5, 0.5, 1), np.array([0, -0.15, +0.15, -0.3, 0.3, -0.45, 0.45]),
+                np.array([0.29, 0.27, 0.31, 0.25, 0.23]), np.array([0, -15, +15]) * np.pi / 180,
+                np.array([0, -15, +15]) * np.pi / 180, np.array([0, -22.5, +22.5, -45, +45]) * np.pi / 180,
+            ), axis=-1).reshape(-1, 6)
 
         class curriculum_thresholds(PrefixProto, cli=False):
             cl_fix_target = False
@@ -775,7 +781,9 @@ SUPPORTED = {
     "terrain.valid_tunnel_only": ((False,), "go1_gym/utils/tunnel.py:101-118 (OMPL validity check)"),
     "commands.traj_function": (("fixed_target", "random_target", "random_goal"), "trajectory_function.py:14-93"),
     "commands.traj_length": (tuple(range(1, 17)), "trajectory_function.py:14-93 (<= GO1_MAX_TRAJ)"),
-    "commands.sampling_based_planning": ((False,), ":850-921 (OMPL planner)"),
+    # the in-step planner is plain tensor code over measured_heights (OMPL is only behind valid_tunnel_only); the step
+    # itself does not plan: LeggedRobot runs it as a launch of its own (plan.py) and asks for planner=True below
+    "commands.sampling_based_planning": ((False,), ":850-921 (_plan_target_pose: the env's planner launch, plan.py)"),
     "commands.switch_upon_reach": ((True,), ":836-839"),
     "control.control_type": (("actuator_net",), ":957-996"),
     "domain_rand.lag_timesteps": ((6,), ":973-974"),
@@ -800,9 +808,9 @@ CONTAINERS = {
     "TrajectoryTrackingRewards": dict({k: k for k in _TT}, reaching_linear_vel="exploration_lin",
                                       reaching_yaw="exploration_yaw"),
 }
-# TrajectoryTrackingRewards._reward_reaching_local_goal reads env.replan, which exists only with the
-# sampling-based planner (:861); that planner is not on this path
-_NOT_ON_PATH = {"reaching_local_goal": ":861 (needs the OMPL planner's replan flag)"}
+# TrajectoryTrackingRewards._reward_reaching_local_goal reads env.replan and the local target of the sampling-based
+# planner (:861): the plan would have to run inside the reward sum, that is inside the step kernel
+_NOT_ON_PATH = {"reaching_local_goal": ":861 (needs the planner's replan flag and local target inside the step)"}
 
 
 def reward_slots(cfg, scales=None):
@@ -902,10 +910,13 @@ def traj_draws(cfg):
 TUNNEL_TYPES = ("single_path", "narrow_path", "random_pyramid")
 
 
-def unsupported(cfg):
-    """[(path, value, allowed, reference line)] for every Cfg value the HIP step does not implement."""
+def unsupported(cfg, planner=False):
+    """[(path, value, allowed, reference line)] for every Cfg value the HIP step does not implement; planner=True:
+    the caller runs the local target planner behind the step (plan.py), so sampling_based_planning may be on."""
     bad = []
     for path, (allowed, ref) in SUPPORTED.items():
+        if planner and path == "commands.sampling_based_planning":
+            allowed = (False, True)
         v = _get(cfg, path, allowed[0])
         if isinstance(v, (np.bool_, np.integer)):
             v = v.item()
@@ -917,8 +928,24 @@ def unsupported(cfg):
     return bad
 
 
-def check_supported(cfg):
-    bad = unsupported(cfg)
+def check_planner(cfg):
+    """The Cfg of a planning env (sampling_based_planning = True): raises, with the reference's own cause where it
+    fails itself, before any handle is built."""
+    from . import plan
+    if not bool(_get(cfg, "env.observe_heights", True)):
+        raise TypeError("'int' object is not subscriptable (sampling_based_planning reads measured_heights, which "
+                        "stays 0 without env.observe_heights, :894 and :1218)")
+    if int(_get(cfg, "commands.plan_interval", 10)) <= 0:
+        raise NameError("name 'ep_start' is not defined (Cfg.commands.plan_interval <= 0 with "
+                        "sampling_based_planning, legged_robot_trajectory_tracking.py:867)")
+    if not hasattr(cfg.commands, "candidate_target_poses"):
+        raise AttributeError("type object 'commands' has no attribute 'candidate_target_poses' (:879)")
+    g = scan_grid(cfg)
+    plan.prepare_tables(cfg.commands.candidate_target_poses, g["x"], g["y"])  # shape and caps
+
+
+def check_supported(cfg, planner=False):
+    bad = unsupported(cfg, planner)
     if bad:
         lines = "; ".join(f"Cfg.{p} = {v!r} (implemented: {', '.join(map(repr, a))}; reference {r})"
                           for p, v, a, r in bad)
@@ -955,10 +982,13 @@ def fill_integrator_block(c, cfg, d, physics, n, actuator=None):
         c.actuator[i] = float(v)
 
 
-def build_abi_config(cfg, n_envs=None, physics=None, actuator=None, hf_shape=(80, 40)):
+def build_abi_config(cfg, n_envs=None, physics=None, actuator=None, hf_shape=(80, 40), planner=False):
     """go1_config for the C ABI from a (mutated) Cfg (raises NotImplementedError for any Cfg value
-    the HIP step does not implement, see SUPPORTED)."""
-    check_supported(cfg)
+    the HIP step does not implement, see SUPPORTED).  planner=True: the caller follows each step with the local
+    target planner's launch (plan.py), so Cfg.commands.sampling_based_planning = True is taken and checked."""
+    check_supported(cfg, planner)
+    if planner and bool(_get(cfg, "commands.sampling_based_planning", False)):
+        check_planner(cfg)
     physics = dict(PHYSICS, **(physics or {}))
     d = derived(cfg)
     c = abi.Go1Config()

@@ -289,7 +289,10 @@ class LeggedRobot(EnvBase):
         # the kernels index the tiles as (hf_nx, hf_ny): the Cfg's own tile geometry, not the README's 80 x 40
         plane = cfg.terrain.mesh_type == "plane"
         lay = None if plane else T.tunnel_layout(cfg.terrain)
-        self._abi_cfg = CF.build_abi_config(cfg, n_envs=n, physics=physics,
+        # Cfg.commands.sampling_based_planning: the local target planner's launch follows every step (plan.py)
+        planning = bool(getattr(cfg.commands, "sampling_based_planning", False))
+        self._planner = None
+        self._abi_cfg = CF.build_abi_config(cfg, n_envs=n, physics=physics, planner=planning,
                                             **({} if plane else {"hf_shape": (lay.tile_x, lay.tile_y)}))
         self._abi_cfg.env_id_offset = rank * n
         # terrain: the global grid is built identically on every rank (same seed), each
@@ -317,6 +320,9 @@ class LeggedRobot(EnvBase):
         self._elog = EpisodeLogRing(self, n, dev, compact=self._fast and not self._abi_cfg.indefinite_slots)
         self._prepared = {}
         self._aux = torch.zeros((n, abi.GO1_AUX), device=dev)
+        if planning:
+            from . import plan
+            self._planner = plan.LocalPlanner(self)
         # which per-step outputs the kernel stores beyond obs / rewards / resets (set_output_demand)
         self._demand = (True, True)
         # envs the native integrator's divergence guard reset, cumulative (extras["diverged"])
@@ -421,7 +427,29 @@ class LeggedRobot(EnvBase):
 
     @property
     def commands(self):
+        if self._planner is not None:  # a view of local_relative_linear, as in the reference (:802)
+            return self._planner.local_relative_linear[:, :2]
         return self._aux_view(6, 8)
+
+    def _planner_attr(name):  # noqa: N805 -- the planner's tensors under the reference's names
+        def get(self):
+            if self._planner is None:
+                raise AttributeError(f"{name} exists only with Cfg.commands.sampling_based_planning")
+            return getattr(self._planner, name)
+        return property(get)
+
+    local_target_poses = _planner_attr("local_target_poses")
+    local_relative_linear = _planner_attr("local_relative_linear")
+    local_relative_rotation = _planner_attr("local_relative_rotation")
+    plan_buf = _planner_attr("plan_buf")
+    plan_length_buf = _planner_attr("plan_length_buf")
+    replan = _planner_attr("replan")
+    del _planner_attr
+
+    @property
+    def planner(self):
+        """The LocalPlanner behind this env (chosen, no_valid(), ...), or None when the Cfg does not plan."""
+        return self._planner
 
     @property
     def foot_positions(self):
@@ -462,10 +490,14 @@ class LeggedRobot(EnvBase):
                        time_out=self._time_out[s])
             hist = self._obs_hist[s] if self._obs_hist is not None else None
             cf = {} if self._demand[0] else {"contact_forces": False}
+            if self._planner is not None:
+                cf["debug"] = {"heights": self._planner.heights}
             self._sim.step(a, self._gravity_vec, self._sim_gravity, self._scale_vector(), rng_seed=self.seed,
                            rng_step=self._rng_step, out=out, episode_log=self._elog.next_slot(),
                            aux=self._aux if self._demand[1] else None, obs_history=hist, events=events,
                            diverged_count=self._diverged, **cf)
+        if self._planner is not None:  # the plan launch follows the step kernel on the same stream
+            self._planner.step(out, self._planner.heights, hist, self._aux if self._demand[1] else None)
         if self._rec is not None:  # a recording is armed: its launch follows the step kernel on the same stream
             self._record_step(out["reset"])
         if self._tracer is not None:
@@ -488,7 +520,8 @@ class LeggedRobot(EnvBase):
         args = self._sim.prepare(out, aux=self._aux if self._demand[1] else None, obs_history=hist,
                                  diverged_count=self._diverged, episode_log=log,
                                  log_count=el.count[el.half] if el.compact else None,
-                                 contact_forces=self._demand[0])
+                                 contact_forces=self._demand[0],
+                                 **({} if self._planner is None else {"heights": self._planner.heights}))
         return args, out, hist
 
     def update_curriculum(self):
@@ -515,6 +548,8 @@ class LeggedRobot(EnvBase):
         self._train_ep["episode_length"].extend(ep)
         self._sim.reset_idx(env_ids, rng_seed=self.seed, rng_step=(1 << 62) + self._rng_step)
         self._rng_step += 1
+        if self._planner is not None:
+            self._planner.mark_reset(env_ids)
         if self._tracer is not None:
             self._tracer.mark_reset(env_ids)
         tb = self.time_out_buf[: self.num_train_envs]

@@ -280,9 +280,20 @@ class Go1Native(NativeHandle):
         rs[:len(scales)] = np.asarray(scales, np.float32)
         a.reward_scales[:] = [float(x) for x in rs]
 
-    def _check_optional(self, a, contact_forces, aux, obs_history, diverged_count, episode_log, log_count=None):
+    def _check_heights(self, heights, what="heights"):
+        if tuple(heights.shape) != (self.n, 2, self.cfg.scan_nx, self.cfg.scan_ny) or not heights.is_contiguous() or \
+                heights.dtype != torch.float32 or heights.device != self.device:
+            raise NativeError(f"{what} must be a contiguous (n_envs, 2, {self.cfg.scan_nx}, {self.cfg.scan_ny}) "
+                              f"float32 tensor on the env's device (go1_config.scan_nx x scan_ny)")
+
+    def _check_optional(self, a, contact_forces, aux, obs_history, diverged_count, episode_log, log_count=None,
+                        heights=None):
         """Validate the optional buffers and write their pointers (None -> NULL: the kernel skips that store).
-        `episode_log` with `log_count` selects the compact log (go1_step_args.episode_log_count)."""
+        `episode_log` with `log_count` selects the compact log (go1_step_args.episode_log_count); `heights` receives
+        the step's measured heights (go1_step_args.dbg_heights; the local planner reads them, plan.py)."""
+        if heights is not None:
+            self._check_heights(heights)
+            a.dbg_heights = heights.data_ptr()
         a.contact_forces = self.contact_forces.data_ptr() if contact_forces else None
         if aux is not None and (not aux.is_contiguous() or aux.shape != (self.n, abi.GO1_AUX) or
                                 aux.device != self.device):
@@ -338,11 +349,8 @@ class Go1Native(NativeHandle):
         else:
             a.inj_dof = a.inj_root = a.inj_contact = None
         self._check_out(a, out)
-        if debug and "heights" in debug and (tuple(debug["heights"].shape) !=
-                                             (self.n, 2, self.cfg.scan_nx, self.cfg.scan_ny) or
-                                             not debug["heights"].is_contiguous()):
-            raise NativeError(f"debug heights must be a contiguous (n_envs, 2, {self.cfg.scan_nx}, "
-                              f"{self.cfg.scan_ny}) tensor (go1_config.scan_nx x scan_ny)")
+        if debug and "heights" in debug:
+            self._check_heights(debug["heights"], "debug heights")
         for k, fld in (("torques", "dbg_torques"), ("heights", "dbg_heights"), ("terms", "dbg_terms"),
                        ("commands", "dbg_commands"), ("reached", "dbg_reached")):
             setattr(a, fld, debug[k].data_ptr() if debug and k in debug else None)
@@ -354,15 +362,16 @@ class Go1Native(NativeHandle):
 
     # ------------------------------------------------------------------ per-step fast path
     def prepare(self, out, aux=None, obs_history=None, diverged_count=None, episode_log=None, log_count=None,
-                contact_forces=True):
+                contact_forces=True, heights=None):
         """A validated go1_step_args for step_prepared: the env builds one per (output-ring slot,
         episode-log half) once, so the per-step host work is a handful of field writes and the
         ctypes call (the loop is otherwise host-bound at ~60 us per step).  `episode_log` with
         `log_count` selects the compact log (go1_step_args.episode_log_count); contact_forces=False
-        leaves the contact-force store out."""
+        leaves the contact-force store out; `heights` (n_envs, 2, scan_nx, scan_ny) has the kernel store its measured
+        heights (go1_step_args.dbg_heights), which it does not do otherwise."""
         a = self._new_args()
         self._check_out(a, out)
-        self._check_optional(a, contact_forces, aux, obs_history, diverged_count, episode_log, log_count)
+        self._check_optional(a, contact_forces, aux, obs_history, diverged_count, episode_log, log_count, heights)
         return a
 
     def step_prepared(self, a, actions, gravity_vec, sim_gravity, reward_scales, consts_key, rng_seed, rng_step,
