@@ -31,6 +31,9 @@ LIBS = {
     # the local target planner (plan.py): one launch after the step kernel, built as the step kernels are because it
     # shares their torch-order math (go1_torch_math.h) bit for bit; no file in common with the render / trace libraries
     "libgo1_plan.so": (["go1_plan.hip"], STEP_FLAGS),
+    # the after-start domain randomiser (randomize.py): one launch after the step kernel, built with the planner's
+    # flags: it uses the step kernels' Philox and clampf, and its u * range + lo must stay a multiply and an add
+    "libgo1_dr.so": (["go1_dr.hip"], STEP_FLAGS),
     # test-only: one thin kernel per device function of go1_device.h (tests/devcheck.py), built as the step kernels are
     "libgo1_devcheck.so": (["go1_devcheck.hip"], STEP_FLAGS),
 }

@@ -789,8 +789,10 @@ SUPPORTED = {
     "domain_rand.lag_timesteps": ((6,), ":973-974"),
     "domain_rand.randomize_lag_timesteps": ((True,), ":973-974"),
     "domain_rand.randomize_com_displacement": ((False,), ":735-742"),
-    "domain_rand.push_robots": ((False,), ":1055-1071"),
-    "domain_rand.randomize_rigids_after_start": ((False,), ":226-228"),
+    # neither runs in the step: the envs follow it with the randomiser's launch (randomize.py), randomizer=True below
+    "domain_rand.push_robots": ((False,), ":1074-1084 (_push_robots: the env's randomiser launch, randomize.py)"),
+    "domain_rand.randomize_rigids_after_start": ((False,), ":233-235, :831-833 (the env's randomiser launch, "
+                                                           "randomize.py)"),
     "curriculum_thresholds.cl_fix_target": ((False,), ":188-196"),
 }
 
@@ -910,12 +912,19 @@ def traj_draws(cfg):
 TUNNEL_TYPES = ("single_path", "narrow_path", "random_pyramid")
 
 
-def unsupported(cfg, planner=False):
+_RANDOMIZER_PATHS = ("domain_rand.push_robots", "domain_rand.randomize_rigids_after_start")
+
+
+def unsupported(cfg, planner=False, randomizer=False):
     """[(path, value, allowed, reference line)] for every Cfg value the HIP step does not implement; planner=True:
-    the caller runs the local target planner behind the step (plan.py), so sampling_based_planning may be on."""
+    the caller runs the local target planner behind the step (plan.py), so sampling_based_planning may be on;
+    randomizer=True: the caller runs the after-start randomiser behind the step (randomize.py), so push_robots and
+    randomize_rigids_after_start may be on."""
     bad = []
     for path, (allowed, ref) in SUPPORTED.items():
         if planner and path == "commands.sampling_based_planning":
+            allowed = (False, True)
+        if randomizer and path in _RANDOMIZER_PATHS:
             allowed = (False, True)
         v = _get(cfg, path, allowed[0])
         if isinstance(v, (np.bool_, np.integer)):
@@ -944,8 +953,8 @@ def check_planner(cfg):
     plan.prepare_tables(cfg.commands.candidate_target_poses, g["x"], g["y"])  # shape and caps
 
 
-def check_supported(cfg, planner=False):
-    bad = unsupported(cfg, planner)
+def check_supported(cfg, planner=False, randomizer=False):
+    bad = unsupported(cfg, planner, randomizer)
     if bad:
         lines = "; ".join(f"Cfg.{p} = {v!r} (implemented: {', '.join(map(repr, a))}; reference {r})"
                           for p, v, a, r in bad)
@@ -982,13 +991,19 @@ def fill_integrator_block(c, cfg, d, physics, n, actuator=None):
         c.actuator[i] = float(v)
 
 
-def build_abi_config(cfg, n_envs=None, physics=None, actuator=None, hf_shape=(80, 40), planner=False):
+def build_abi_config(cfg, n_envs=None, physics=None, actuator=None, hf_shape=(80, 40), planner=False,
+                     randomizer=False):
     """go1_config for the C ABI from a (mutated) Cfg (raises NotImplementedError for any Cfg value
     the HIP step does not implement, see SUPPORTED).  planner=True: the caller follows each step with the local
-    target planner's launch (plan.py), so Cfg.commands.sampling_based_planning = True is taken and checked."""
-    check_supported(cfg, planner)
+    target planner's launch (plan.py), so Cfg.commands.sampling_based_planning = True is taken and checked.
+    randomizer=True: the caller follows each step with the after-start randomiser's launch (randomize.py), so
+    Cfg.domain_rand.push_robots and randomize_rigids_after_start are taken and checked."""
+    check_supported(cfg, planner, randomizer)
     if planner and bool(_get(cfg, "commands.sampling_based_planning", False)):
         check_planner(cfg)
+    if randomizer and any(bool(_get(cfg, p, False)) for p in _RANDOMIZER_PATHS):
+        from . import randomize
+        randomize.check_randomizer(cfg)
     physics = dict(PHYSICS, **(physics or {}))
     d = derived(cfg)
     c = abi.Go1Config()

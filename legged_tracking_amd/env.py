@@ -30,8 +30,9 @@ Differences from the reference, all documented in DESIGN.md:
     actors, num_actor = 2); the arrow actor is visual only;
   * extras["time_outs"] exists from the first step (all False until the first
     reset), which is numerically identical for PPO's bootstrapping (adds 0);
-  * eval envs (eval_cfg), curriculum (cl_fix_target), push_robots and
-    randomize_rigids_after_start are not on this path and raise.
+  * eval envs (eval_cfg) and the curriculum (cl_fix_target) are not on this path and raise;
+  * push_robots and randomize_rigids_after_start run as one launch behind the step kernel
+    (randomize.py), not inside the step.
 """
 from collections import defaultdict, deque
 
@@ -274,9 +275,6 @@ class LeggedRobot(EnvBase):
             raise NotImplementedError("eval envs (eval_cfg) are not on the accelerated path")
         if cfg.curriculum_thresholds.cl_fix_target:
             raise NotImplementedError("cl_fix_target curriculum is not on the accelerated path")
-        dr = cfg.domain_rand
-        if getattr(dr, "push_robots", False) or getattr(dr, "randomize_rigids_after_start", False):
-            raise NotImplementedError("push_robots / randomize_rigids_after_start are not on the accelerated path")
         d = CF.derived(cfg)
         self._init_dims(cfg, d, sim_device, headless, seed, rank, world_size)
         rank = self.rank
@@ -292,7 +290,10 @@ class LeggedRobot(EnvBase):
         # Cfg.commands.sampling_based_planning: the local target planner's launch follows every step (plan.py)
         planning = bool(getattr(cfg.commands, "sampling_based_planning", False))
         self._planner = None
-        self._abi_cfg = CF.build_abi_config(cfg, n_envs=n, physics=physics, planner=planning,
+        # Cfg.domain_rand.push_robots / randomize_rigids_after_start: the randomiser's launch follows every step
+        # (randomize.py); the Cfg is checked here, before a handle is built
+        self._randomizer = None
+        self._abi_cfg = CF.build_abi_config(cfg, n_envs=n, physics=physics, planner=planning, randomizer=True,
                                             **({} if plane else {"hf_shape": (lay.tile_x, lay.tile_y)}))
         self._abi_cfg.env_id_offset = rank * n
         # terrain: the global grid is built identically on every rank (same seed), each
@@ -323,6 +324,7 @@ class LeggedRobot(EnvBase):
         if planning:
             from . import plan
             self._planner = plan.LocalPlanner(self)
+        self._init_randomizer()
         # which per-step outputs the kernel stores beyond obs / rewards / resets (set_output_demand)
         self._demand = (True, True)
         # envs the native integrator's divergence guard reset, cumulative (extras["diverged"])
@@ -496,6 +498,8 @@ class LeggedRobot(EnvBase):
                            rng_step=self._rng_step, out=out, episode_log=self._elog.next_slot(),
                            aux=self._aux if self._demand[1] else None, obs_history=hist, events=events,
                            diverged_count=self._diverged, **cf)
+        if self._randomizer is not None:  # pushes and rigid props: the first launch behind the step kernel
+            self._randomizer.step(out["reset"], out["priv"], self._rng_step)
         if self._planner is not None:  # the plan launch follows the step kernel on the same stream
             self._planner.step(out, self._planner.heights, hist, self._aux if self._demand[1] else None)
         if self._rec is not None:  # a recording is armed: its launch follows the step kernel on the same stream
@@ -547,6 +551,8 @@ class LeggedRobot(EnvBase):
             self._train_ep["rew_" + key].extend(sums[:, i])
         self._train_ep["episode_length"].extend(ep)
         self._sim.reset_idx(env_ids, rng_seed=self.seed, rng_step=(1 << 62) + self._rng_step)
+        if self._randomizer is not None:
+            self._randomizer.reset_idx(env_ids, (1 << 62) + self._rng_step)
         self._rng_step += 1
         if self._planner is not None:
             self._planner.mark_reset(env_ids)

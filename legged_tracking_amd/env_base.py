@@ -229,6 +229,35 @@ class EnvBase:
     def dof_vel(self):
         return self._sim.state["dof_vel"]
 
+    # ------------------------------------------------------------------ after-start randomiser (randomize.py)
+    # With Cfg.domain_rand.push_robots or randomize_rigids_after_start, step() issues the randomiser's launch right
+    # after the step kernel and reset_idx its redraw; with both off nothing is built and nothing is launched.
+    _randomizer = None
+
+    def _init_randomizer(self):
+        from . import randomize
+        if randomize.wanted(self.cfg):
+            self._randomizer = randomize.Randomizer(self)
+
+    @property
+    def randomizer(self):
+        """The Randomizer behind this env, or None when the Cfg sets neither of its flags."""
+        return self._randomizer
+
+    @property
+    def friction_coeffs(self):
+        return self._sim.state["friction"]
+
+    @property
+    def restitutions(self):
+        return self._sim.state["restitution"]
+
+    @property
+    def payloads(self):
+        """The reference's tensor of that name: it follows the redraws after start, while the simulated mass (the
+        payload plane) stays the creation-time one, as PhysX keeps it."""
+        return self._randomizer.payloads if self._randomizer is not None else self._sim.state["payload"]
+
     def get_observations(self):
         return self.obs_buf
 

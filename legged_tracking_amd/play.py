@@ -24,9 +24,11 @@ import torch
 from . import checkpoint as CK, config as CF, policy_kernels as PK, video
 from .env import HistoryWrapper, TrajectoryTrackingEnv
 
-# scripts/eval.py:89-101
-DR_OFF = ("push_robots", "randomize_friction", "randomize_gravity", "randomize_restitution", "randomize_motor_offset",
-          "randomize_motor_strength", "randomize_friction_indep", "randomize_ground_friction", "randomize_base_mass",
+# scripts/eval.py:89-101, and randomize_rigids_after_start: eval.py leaves it on, where it redraws nothing once every
+# randomize_* flag below is off; here it would still cost the randomiser's launch behind every step
+DR_OFF = ("push_robots", "randomize_rigids_after_start", "randomize_friction", "randomize_gravity",
+          "randomize_restitution", "randomize_motor_offset", "randomize_motor_strength",
+          "randomize_friction_indep", "randomize_ground_friction", "randomize_base_mass",
           "randomize_Kd_factor", "randomize_Kp_factor", "randomize_joint_friction", "randomize_com_displacement")
 
 

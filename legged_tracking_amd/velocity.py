@@ -23,7 +23,7 @@ import os
 import numpy as np
 import torch
 
-from . import abi, config as CF, layout as L, vel_abi as VA, vel_layout as VL, velocity_config as V
+from . import abi, config as CF, layout as L, randomize as RZ, vel_abi as VA, vel_layout as VL, velocity_config as V
 from .env_base import OUT_RING, EnvBase, StepExtras  # noqa: F401  (OUT_RING: importable from here)
 from .native import NativeError, NativeHandle, load_library  # noqa: F401  (NativeError: the one class)
 
@@ -59,9 +59,10 @@ def lib():
 PHYSICS = dict(CF.PHYSICS)
 
 
-def unsupported(cfg):
+def unsupported(cfg, randomizer=False):
     """Cfg values of the velocity env the HIP step does not implement (each raises NotImplementedError
-    at construction instead of training on something else)."""
+    at construction instead of training on something else).  randomizer=True: the caller follows each step with the
+    after-start randomiser's launch (randomize.py), so push_robots and randomize_rigids_after_start may be on."""
     bad = []
     e, t, c, r, dr, ctl = cfg.env, cfg.terrain, cfg.commands, cfg.rewards, cfg.domain_rand, cfg.control
     if t.mesh_type != "plane":
@@ -95,6 +96,8 @@ def unsupported(cfg):
         bad.append("domain_rand lag (randomize_lag_timesteps with lag_timesteps 6)")
     for k in ("push_robots", "randomize_rigids_after_start", "randomize_com_displacement", "randomize_Kp_factor",
               "randomize_Kd_factor", "randomize_friction_indep"):
+        if randomizer and k in ("push_robots", "randomize_rigids_after_start"):
+            continue
         if getattr(dr, k, False):
             bad.append(f"domain_rand.{k}")
     if t.teleport_robots:
@@ -109,12 +112,15 @@ def unsupported(cfg):
     return bad
 
 
-def build_configs(cfg, n_envs=None, physics=None, env_id_offset=0, history_len=None):
+def build_configs(cfg, n_envs=None, physics=None, env_id_offset=0, history_len=None, randomizer=False):
     """(go1_config for the integrator / actuator, go1_vel_config, curriculum grid (15, n_bins) f64, initial
-    weights (n_bins,) f64) for a velocity Cfg; raises NotImplementedError for unsupported values."""
-    bad = unsupported(cfg)
+    weights (n_bins,) f64) for a velocity Cfg; raises NotImplementedError for unsupported values.  randomizer=True:
+    push_robots and randomize_rigids_after_start are taken and checked (the caller runs randomize.py's launch)."""
+    bad = unsupported(cfg, randomizer)
     if bad:
         raise NotImplementedError("velocity step: unsupported configuration: " + "; ".join(bad))
+    if randomizer and RZ.wanted(cfg):
+        RZ.check_randomizer(cfg)
     physics = dict(PHYSICS, **(physics or {}))
     d = V.vel_derived(cfg)
     n = int(n_envs if n_envs is not None else cfg.env.num_envs)
@@ -306,7 +312,7 @@ class VelocityTrackingEasyEnv(EnvBase):
         self._init_dims(cfg, V.vel_derived(cfg), sim_device, headless, seed, rank, world_size)
         rank, n = self.rank, self.num_envs
         self._phys, self._vcfg, grid, w0, self.reward_names, self.command_sum_keys = build_configs(
-            cfg, n_envs=n, physics=physics, env_id_offset=rank * n)
+            cfg, n_envs=n, physics=physics, env_id_offset=rank * n, randomizer=True)
         self.episode_keys = list(self.reward_names) + ["total"]
         self.curriculum_grid = grid
         self.category_names = list(V.CATEGORIES) if cfg.commands.gaitwise_curricula else ["nominal"]
@@ -322,6 +328,7 @@ class VelocityTrackingEasyEnv(EnvBase):
         st["root"][:, :3] = self.env_origins + torch.as_tensor(list(cfg.init_state.pos), device=dev)
         for i, nme in enumerate(L.DOF_NAMES):
             st["dof_pos"][:, i] = float(cfg.init_state.default_joint_angles[nme])
+        self._init_randomizer()
         self._hist = None  # 2 wide (n, 70 x (history + HIST_WINDOW)) buffers when a HistoryWrapper attaches
         self._hist_buf, self._hist_off = 0, 0  # buffer and window (in observations) of the last returned history
         # compact episode log: one row per reset env (n_terms + 1 sums, tag, env)
@@ -443,6 +450,8 @@ class VelocityTrackingEasyEnv(EnvBase):
         events = self.kernel_events.popleft() if self.kernel_events else None
         args.ev_begin, args.ev_end = events if events is not None else (None, None)
         self._sim.step(args)
+        if self._randomizer is not None:  # pushes and rigid props: behind the step's curriculum launch
+            self._randomizer.step(self._reset[s], self._priv[s], self._rng_step)
         if self._rec is not None:  # a recording is armed: its launch follows the step's launches on the same stream
             self._record_step(self._reset[s])
         if self._tracer is not None:
@@ -509,6 +518,8 @@ class VelocityTrackingEasyEnv(EnvBase):
         self._log_tag += 1
         self._sim.reset_idx(env_ids, rng_seed=self.seed, rng_step=(1 << 62) + self._rng_step, log=self._log,
                             log_count=self._log_count, log_tag=self._log_tag)
+        if self._randomizer is not None:
+            self._randomizer.reset_idx(env_ids, (1 << 62) + self._rng_step)
         self._rng_step += 1
         if self._tracer is not None:
             self._tracer.mark_reset(env_ids)
