@@ -29,7 +29,7 @@ LIBS = {
     # the episode tracer (trace.py): a library of its own, so the render and step ABIs and their size checks stay put
     "libgo1_trace.so": (["go1_trace.hip"], []),
     # the local target planner (plan.py): one launch after the step kernel, built as the step kernels are because it
-    # shares their torch-order math (go1_torch_math.h) bit for bit; no file in common with the render / trace libraries
+    # shares their torch-order math (go1_torch_math.h) bit for bit; with the render / trace libraries it has only go1_host.h in common
     "libgo1_plan.so": (["go1_plan.hip"], STEP_FLAGS),
     # the after-start domain randomiser (randomize.py): one launch after the step kernel, built with the planner's
     # flags: it uses the step kernels' Philox and clampf, and its u * range + lo must stay a multiply and an add

@@ -4,22 +4,15 @@
 // due; with rand_interval and push_interval in the hundreds that is almost every lane, so almost every wave ends after
 // those two loads.  A due lane evaluates one Philox block per kind of work it has (rigid props, push), with the step
 // kernels' generator (go1_lanes.h), and writes its few values with plain stores.  u * range + lo is a multiply and an
-// add (contraction off, as in the step kernels), and the privileged observation uses their clampf.
-#include <stdio.h>
-
+// add (contraction off, as in the step kernels), and the privileged observation uses their clampf.  The error message
+// and the launch check are go1_host.h's, shared with the other add-on libraries.
 #include "../../include/go1_dr.h"
 #include "go1_device.h"
+#include "go1_host.h"
 
 namespace {
 
 constexpr int THREADS = 256;
-
-thread_local char g_err[256] = "";
-
-int fail(const char* fn, const char* msg) {
-  snprintf(g_err, sizeof g_err, "%s: %s", fn, msg);
-  return -1;
-}
 
 struct Params {
   go1_dr_config c;
@@ -109,23 +102,14 @@ __global__ __launch_bounds__(THREADS) void go1_dr_reset_kernel(const go1_dr_conf
 }
 
 int check_cfg(const char* fn, const go1_dr_config* c, const go1_dr_state* s) {
-  if (c->n_envs < 1) return fail(fn, "n_envs must be >= 1");
-  if (c->env_id_offset < 0) return fail(fn, "env_id_offset must be >= 0");
-  if (c->rand_interval < 1) return fail(fn, "rand_interval must be >= 1");
-  if (c->push_interval < 1) return fail(fn, "push_interval must be >= 1");
+  if (c->n_envs < 1) return fail("%s: n_envs must be >= 1", fn);
+  if (c->env_id_offset < 0) return fail("%s: env_id_offset must be >= 0", fn);
+  if (c->rand_interval < 1) return fail("%s: rand_interval must be >= 1", fn);
+  if (c->push_interval < 1) return fail("%s: push_interval must be >= 1", fn);
   if (!(c->payload_range >= 0.0f) || !(c->friction_range >= 0.0f) || !(c->restitution_range >= 0.0f) ||
       !(c->push_range >= 0.0f))
-    return fail(fn, "every range must be >= 0");
-  if (!s->root || !s->friction || !s->restitution) return fail(fn, "state: root, friction and restitution must be set");
-  return 0;
-}
-
-int launched(const char* fn) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof g_err, "%s: launch failed: %s", fn, hipGetErrorString(e));
-    return -1;
-  }
+    return fail("%s: every range must be >= 0", fn);
+  if (!s->root || !s->friction || !s->restitution) return fail("%s: state: root, friction and restitution must be set", fn);
   return 0;
 }
 
@@ -142,14 +126,14 @@ void go1_dr_abi_sizes(int64_t out[4]) {
   out[3] = GO1_DR_U;
 }
 
-const char* go1_dr_last_error(void) { return g_err; }
+GO1_LAST_ERROR(go1_dr)
 
 int go1_dr_step(const go1_dr_config* c, const go1_dr_state* s, const go1_dr_args* a, void* stream) {
   const char* fn = "go1_dr_step";
-  if (!c || !s || !a) return fail(fn, "null cfg, state or args");
+  if (!c || !s || !a) return fail("%s: null cfg, state or args", fn);
   if (check_cfg(fn, c, s)) return -1;
-  if (!a->reset || !a->episode_length) return fail(fn, "args: reset and episode_length must be set");
-  if (a->priv && a->priv_stride < 2) return fail(fn, "priv_stride must be >= 2 (friction, restitution)");
+  if (!a->reset || !a->episode_length) return fail("%s: args: reset and episode_length must be set", fn);
+  if (a->priv && a->priv_stride < 2) return fail("%s: priv_stride must be >= 2 (friction, restitution)", fn);
   if (!c->rigids_after_start && !c->push_robots) return 0;  // nothing to do: no launch
   Params p;
   p.c = *c;
@@ -163,10 +147,10 @@ int go1_dr_step(const go1_dr_config* c, const go1_dr_state* s, const go1_dr_args
 int go1_dr_reset(const go1_dr_config* c, const go1_dr_state* s, const int32_t* ids, int32_t n_ids, uint64_t rng_step,
                  const float* uniforms, void* stream) {
   const char* fn = "go1_dr_reset";
-  if (!c || !s) return fail(fn, "null cfg or state");
+  if (!c || !s) return fail("%s: null cfg or state", fn);
   if (check_cfg(fn, c, s)) return -1;
-  if (n_ids < 0) return fail(fn, "n_ids must be >= 0");
-  if (n_ids > 0 && !ids) return fail(fn, "ids must be set");
+  if (n_ids < 0) return fail("%s: n_ids must be >= 0", fn);
+  if (n_ids > 0 && !ids) return fail("%s: ids must be set", fn);
   if (n_ids == 0 || !c->rigids_after_start) return 0;
   const unsigned blocks = ((unsigned)n_ids + THREADS - 1) / THREADS;
   hipLaunchKernelGGL(go1_dr_reset_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream, *c, *s, ids, (int)n_ids,

@@ -11,24 +11,17 @@
 //      footprint; a wave reduces with lane shuffles, the four waves through LDS.  No sort: the minimum of
 //      (key, index) is the first valid entry of a stable argsort by key.
 // The relative poses use the step kernel's own functions (go1_torch_math.h, contraction off), so a local target
-// equal to the global one gives the commands the step kernel wrote, bit for bit.
-#include <stdio.h>
-
+// equal to the global one gives the commands the step kernel wrote, bit for bit.  The error message and the launch
+// check are go1_host.h's, shared with the other add-on libraries.
 #include "../../include/go1_plan.h"
 #include "go1_device.h"
+#include "go1_host.h"
 
 namespace {
 
 constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / 64;
 constexpr int MAX_PTS = GO1_PLAN_MAX_X * GO1_PLAN_MAX_Y;
-
-thread_local char g_err[256] = "";
-
-int fail(const char* msg) {
-  snprintf(g_err, sizeof g_err, "go1_plan_step: %s", msg);
-  return -1;
-}
 
 struct Params {
   go1_plan_config c;
@@ -248,42 +241,37 @@ void go1_plan_abi_sizes(int64_t out[6]) {
   out[5] = GO1_PLAN_FOOT;
 }
 
-const char* go1_plan_last_error(void) { return g_err; }
+GO1_LAST_ERROR(go1_plan)
 
 int go1_plan_step(const go1_plan_config* c, const go1_plan_tables* t, const go1_plan_state* s, const go1_plan_args* a,
                   void* stream) {
-  if (!c || !t || !s || !a) return fail("null cfg, tables, state or args");
-  if (c->n_envs < 1) return fail("n_envs must be >= 1");
-  if (c->traj_length < 1 || c->traj_length > GO1_MAX_TRAJ) return fail("traj_length must be in 1 .. GO1_MAX_TRAJ");
+  if (!c || !t || !s || !a) return fail("go1_plan_step: null cfg, tables, state or args");
+  if (c->n_envs < 1) return fail("go1_plan_step: n_envs must be >= 1");
+  if (c->traj_length < 1 || c->traj_length > GO1_MAX_TRAJ) return fail("go1_plan_step: traj_length must be in 1 .. GO1_MAX_TRAJ");
   if (c->plan_interval < 1)
-    return fail("plan_interval must be >= 1 (the reference raises NameError: ep_start, :867)");
+    return fail("go1_plan_step: plan_interval must be >= 1 (the reference raises NameError: ep_start, :867)");
   if (c->scan_nx < 1 || c->scan_nx > GO1_PLAN_MAX_X || c->scan_ny < 1 || c->scan_ny > GO1_PLAN_MAX_Y)
-    return fail("scan_nx x scan_ny must be within 1 x 1 .. GO1_PLAN_MAX_X x GO1_PLAN_MAX_Y");
-  if (c->n_cand < 1 || c->n_cand > GO1_PLAN_MAX_CAND) return fail("n_cand must be in 1 .. GO1_PLAN_MAX_CAND");
-  if (c->n_foot < 1 || c->n_foot > c->n_cand) return fail("n_foot must be in 1 .. n_cand");
+    return fail("go1_plan_step: scan_nx x scan_ny must be within 1 x 1 .. GO1_PLAN_MAX_X x GO1_PLAN_MAX_Y");
+  if (c->n_cand < 1 || c->n_cand > GO1_PLAN_MAX_CAND) return fail("go1_plan_step: n_cand must be in 1 .. GO1_PLAN_MAX_CAND");
+  if (c->n_foot < 1 || c->n_foot > c->n_cand) return fail("go1_plan_step: n_foot must be in 1 .. n_cand");
   for (int i = 0; i < 3; ++i)
-    if (!(c->robot_size[i] > 0.0f)) return fail("robot_size must be positive");
+    if (!(c->robot_size[i] > 0.0f)) return fail("go1_plan_step: robot_size must be positive");
   if (!t->cand || !t->cand_foot || !t->key_rot || !t->foot)
-    return fail("tables: cand, cand_foot, key_rot and foot must be set");
+    return fail("go1_plan_step: tables: cand, cand_foot, key_rot and foot must be set");
   if (!s->local_target || !s->plan_buf || !s->plan_length || !s->idx_prev || !s->ep_prev || !s->local_rel_lin || !s->local_rel_rot ||
       !s->replan || !s->chosen || !s->no_valid_count)
-    return fail("state: every pointer must be set");
+    return fail("go1_plan_step: state: every pointer must be set");
   if (!a->root || !a->trajectory || !a->curr_pose_index || !a->episode_length || !a->reset || !a->heights || !a->obs)
-    return fail("args: root, trajectory, curr_pose_index, episode_length, reset, heights and obs must be set");
-  if (a->obs_stride < 5) return fail("obs_stride must be >= 5 (the commands are columns 3 and 4)");
-  if (a->commands && a->commands_stride < 2) return fail("commands_stride must be >= 2");
+    return fail("go1_plan_step: args: root, trajectory, curr_pose_index, episode_length, reset, heights and obs must be set");
+  if (a->obs_stride < 5) return fail("go1_plan_step: obs_stride must be >= 5 (the commands are columns 3 and 4)");
+  if (a->commands && a->commands_stride < 2) return fail("go1_plan_step: commands_stride must be >= 2");
   Params p;
   p.c = *c;
   p.t = *t;
   p.s = *s;
   p.a = *a;
   hipLaunchKernelGGL(go1_plan_step_kernel, dim3((unsigned)c->n_envs), dim3(THREADS), 0, (hipStream_t)stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof g_err, "go1_plan_step: launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return launched("go1_plan_step");
 }
 
 }  // extern "C"

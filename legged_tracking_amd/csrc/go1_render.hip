@@ -13,20 +13,11 @@
 //  * every cell index is clamped to [0, n - 2] as a float before its conversion and again as an integer before the
 //    loads (cell_h), env ids, tile ids, marker counts and the frame slot are clamped integers;
 //  * every hit test has the form (t > 0 && t < best), false for a NaN.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-
+// The error message and the launch check are go1_host.h's, shared with the other add-on libraries.
 #include "../../include/go1_render.h"
+#include "go1_host.h"
 
 namespace {
-
-thread_local char g_err[256] = "";
-
-int fail(const char* msg) {
-  snprintf(g_err, sizeof g_err, "%s", msg);
-  return -1;
-}
 
 constexpr int TILE = 16;
 constexpr int NPRIM = 17;
@@ -494,12 +485,7 @@ int launch(Params& p, void* stream) {
   }
   dim3 grid((a.width + TILE - 1) / TILE, (a.height + TILE - 1) / TILE, a.n_views), block(TILE, TILE, 1);
   hipLaunchKernelGGL(render_kernel, grid, block, lds, (hipStream_t)stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof g_err, "go1_render: launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return launched("go1_render");
 }
 
 }  // namespace
@@ -515,7 +501,7 @@ void go1_render_abi_sizes(int64_t out[4]) {
   out[3] = sizeof(go1_record_args);
 }
 
-const char* go1_render_last_error(void) { return g_err; }
+GO1_LAST_ERROR(go1_render)
 
 int go1_render(const go1_render_args* args, void* stream) {
   if (check_args(args)) return -1;

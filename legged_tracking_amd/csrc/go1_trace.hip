@@ -9,12 +9,10 @@
 // the capture slot, and the whole workgroup walks the kept rows x 26 words (and the trajectory) of each ended env,
 // four loads in flight per lane, so a burst in which every env ends (the first time-out of an evaluation) is
 // copied at full width.  The barrier behind the episode path orders its ring reads before the stores that
-// overwrite ring[push % depth] for the same envs.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-
+// overwrite ring[push % depth] for the same envs.  The error message and the launch check are go1_host.h's, shared
+// with the other add-on libraries.
 #include "../../include/go1_trace.h"
+#include "go1_host.h"
 
 namespace {
 
@@ -22,13 +20,6 @@ constexpr int THREADS = 256;
 constexpr int ENVS = 32;
 constexpr int ROW = GO1_TRACE_ROW;
 constexpr int WORDS = (ENVS * ROW + THREADS - 1) / THREADS;  // ring words per lane and push
-
-thread_local char g_err[256] = "";
-
-int fail(const char* msg) {
-  snprintf(g_err, sizeof g_err, "%s", msg);
-  return -1;
-}
 
 struct Params {
   go1_trace_args a;
@@ -157,7 +148,7 @@ void go1_trace_abi_sizes(int64_t out[3]) {
   out[2] = GO1_TRACE_META;
 }
 
-const char* go1_trace_last_error(void) { return g_err; }
+GO1_LAST_ERROR(go1_trace)
 
 int go1_trace_push(const go1_trace_args* a, void* stream) {
   if (!a) return fail("go1_trace_push: null args");
@@ -175,12 +166,7 @@ int go1_trace_push(const go1_trace_args* a, void* stream) {
   p.cur = (uint32_t)(a->push % (uint64_t)a->depth);
   const unsigned grid = ((unsigned)a->n_envs + ENVS - 1) / ENVS;
   hipLaunchKernelGGL(go1_trace_push_kernel, dim3(grid), dim3(THREADS), 0, (hipStream_t)stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof g_err, "go1_trace_push: launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
+  return launched("go1_trace_push");
 }
 
 }  // extern "C"

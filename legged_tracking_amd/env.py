@@ -32,7 +32,7 @@ Differences from the reference, all documented in DESIGN.md:
     reset), which is numerically identical for PPO's bootstrapping (adds 0);
   * eval envs (eval_cfg) and the curriculum (cl_fix_target) are not on this path and raise;
   * push_robots and randomize_rigids_after_start run as one launch behind the step kernel
-    (randomize.py), not inside the step.
+    (randomize.py), not inside the step; EnvBase issues it with the other add-on launches (_after_step).
 """
 from collections import defaultdict, deque
 
@@ -289,10 +289,8 @@ class LeggedRobot(EnvBase):
         lay = None if plane else T.tunnel_layout(cfg.terrain)
         # Cfg.commands.sampling_based_planning: the local target planner's launch follows every step (plan.py)
         planning = bool(getattr(cfg.commands, "sampling_based_planning", False))
-        self._planner = None
         # Cfg.domain_rand.push_robots / randomize_rigids_after_start: the randomiser's launch follows every step
         # (randomize.py); the Cfg is checked here, before a handle is built
-        self._randomizer = None
         self._abi_cfg = CF.build_abi_config(cfg, n_envs=n, physics=physics, planner=planning, randomizer=True,
                                             **({} if plane else {"hf_shape": (lay.tile_x, lay.tile_y)}))
         self._abi_cfg.env_id_offset = rank * n
@@ -488,8 +486,7 @@ class LeggedRobot(EnvBase):
             self._sim.step_prepared(args, a, gvec, sgrav, scales, ck, self.seed, self._rng_step, events=events,
                                     log_tag=el.slot)
         else:
-            out = dict(obs=self._obs[s], priv=self._priv[s], rew=self._rew[s], reset=self._reset[s],
-                       time_out=self._time_out[s])
+            out = self._out[s]
             hist = self._obs_hist[s] if self._obs_hist is not None else None
             cf = {} if self._demand[0] else {"contact_forces": False}
             if self._planner is not None:
@@ -498,14 +495,7 @@ class LeggedRobot(EnvBase):
                            rng_step=self._rng_step, out=out, episode_log=self._elog.next_slot(),
                            aux=self._aux if self._demand[1] else None, obs_history=hist, events=events,
                            diverged_count=self._diverged, **cf)
-        if self._randomizer is not None:  # pushes and rigid props: the first launch behind the step kernel
-            self._randomizer.step(out["reset"], out["priv"], self._rng_step)
-        if self._planner is not None:  # the plan launch follows the step kernel on the same stream
-            self._planner.step(out, self._planner.heights, hist, self._aux if self._demand[1] else None)
-        if self._rec is not None:  # a recording is armed: its launch follows the step kernel on the same stream
-            self._record_step(out["reset"])
-        if self._tracer is not None:
-            self._tracer.push(out["reset"], out["time_out"])
+        self._after_step(out, hist)
         self._last_hist = hist
         self._rng_step += 1
         self._elog.advance()
@@ -517,8 +507,7 @@ class LeggedRobot(EnvBase):
 
     def _prepare_slot(self, s, log):
         """Validated go1_step_args for output-ring slot s and this episode-log buffer."""
-        out = dict(obs=self._obs[s], priv=self._priv[s], rew=self._rew[s], reset=self._reset[s],
-                   time_out=self._time_out[s])
+        out = self._out[s]
         hist = self._obs_hist[s] if self._obs_hist is not None else None
         el = self._elog
         args = self._sim.prepare(out, aux=self._aux if self._demand[1] else None, obs_history=hist,
@@ -551,13 +540,8 @@ class LeggedRobot(EnvBase):
             self._train_ep["rew_" + key].extend(sums[:, i])
         self._train_ep["episode_length"].extend(ep)
         self._sim.reset_idx(env_ids, rng_seed=self.seed, rng_step=(1 << 62) + self._rng_step)
-        if self._randomizer is not None:
-            self._randomizer.reset_idx(env_ids, (1 << 62) + self._rng_step)
+        self._after_reset_idx(env_ids, (1 << 62) + self._rng_step)
         self._rng_step += 1
-        if self._planner is not None:
-            self._planner.mark_reset(env_ids)
-        if self._tracer is not None:
-            self._tracer.mark_reset(env_ids)
         tb = self.time_out_buf[: self.num_train_envs]
         self._timeouts.extend(tb.cpu().numpy())
         self._sim.extras_time_outs.copy_(tb)  # extras["time_outs"] rebinding (:289-291)

@@ -1,9 +1,10 @@
 """What the trajectory env (env.py) and the velocity env (velocity.py) keep on the host in the same way.
 
 EnvBase owns the rank / world-size resolution, dims and seed, the OUT_RING output rings with their *_buf
-views, the state views, the per-env Philox draws keyed by global env id (creation-time domain
+views and per-slot dicts, the state views, the per-env Philox draws keyed by global env id (creation-time domain
 randomisation), the global gravity schedule (_randomize_gravity, _tick_gravity_schedule), the action and
-env-id normalisation, the twelve lazy numpy extras and the reference's recording / render surface (render.py).
+env-id normalisation, the twelve lazy numpy extras, the reference's recording / render surface (render.py) and the
+one path of the add-on launches behind the step kernel and behind a host reset_idx (_after_step, _after_reset_idx).
 
 Each env keeps what differs: when its step ticks the gravity schedule (after the launch / before it, with
 the pre- and post-tick vectors), the initial gravity draw (trajectory only), its aux column layout,
@@ -100,6 +101,9 @@ class EnvBase:
         self._rew = torch.zeros((OUT_RING, n), device=dev)
         self._reset = torch.zeros((OUT_RING, n), dtype=torch.bool, device=dev)
         self._time_out = torch.zeros((OUT_RING, n), dtype=torch.bool, device=dev)
+        # the views of one slot, as a step hands them to the kernel, to the add-ons and to its caller
+        self._out = [dict(obs=self._obs[s], priv=self._priv[s], rew=self._rew[s], reset=self._reset[s],
+                          time_out=self._time_out[s]) for s in range(OUT_RING)]
         self._slot = 0
         self._last_hist = None
         # _randomize_rigid_body_props at creation: per-env draws keyed by GLOBAL env id (every rank draws the
@@ -229,10 +233,37 @@ class EnvBase:
     def dof_vel(self):
         return self._sim.state["dof_vel"]
 
+    # ------------------------------------------------------------------ add-on launches
+    _randomizer = None       # randomize.Randomizer, built by _init_randomizer when the Cfg sets one of its flags
+    _planner = None          # plan.LocalPlanner, built by the trajectory env when its Cfg plans
+
+    def _after_step(self, out, hist):
+        """The add-ons' launches of one step, behind the step kernel on its stream, each only if present: `out` is
+        the step's slot of the output ring, `hist` its copy of obs for the history tap or None.  The order is part of
+        the behaviour: the randomiser rewrites priv before anything reads it, and the planner rewrites obs (and the
+        commands of the trajectory env's aux block) before the recorder or the tracer run."""
+        if self._randomizer is not None:
+            self._randomizer.step(out["reset"], out["priv"], self._rng_step)
+        if self._planner is not None:
+            self._planner.step(out, self._planner.heights, hist, self._aux if self._demand[1] else None)
+        if self._rec is not None:
+            self._record_step(out["reset"])
+        if self._tracer is not None:
+            self._tracer.push(out["reset"], out["time_out"])
+
+    def _after_reset_idx(self, env_ids, rng_step):
+        """What the add-ons are told of a host reset_idx(env_ids), behind the env's own reset launch: the randomiser
+        redraws with the `rng_step` that launch had, the planner and the tracer mark the ended episodes."""
+        if self._randomizer is not None:
+            self._randomizer.reset_idx(env_ids, rng_step)
+        if self._planner is not None:
+            self._planner.mark_reset(env_ids)
+        if self._tracer is not None:
+            self._tracer.mark_reset(env_ids)
+
     # ------------------------------------------------------------------ after-start randomiser (randomize.py)
     # With Cfg.domain_rand.push_robots or randomize_rigids_after_start, step() issues the randomiser's launch right
     # after the step kernel and reset_idx its redraw; with both off nothing is built and nothing is launched.
-    _randomizer = None
 
     def _init_randomizer(self):
         from . import randomize
@@ -285,8 +316,8 @@ class EnvBase:
     # ------------------------------------------------------------------ misc API
     # ------------------------------------------------------------------ recording and rendering (render.py)
     # legged_robot_trajectory_tracking.py:1690-1711, :1775-1806.  Nothing is allocated or launched until the first
-    # start_recording / render call; while a recording is armed, step() issues one recording launch after the step
-    # kernel (_record_step), which reads the state planes and the step's reset output only.
+    # start_recording / render call; while a recording is armed, _after_step issues one recording launch
+    # (_record_step), which reads the state planes and the step's reset output only.
     renderer_factory = None  # tests inject a test double; None: render.Renderer
     _renderer = None         # created on first use
     _rec = None              # the renderer while record_now is set (:1777), else None
@@ -331,8 +362,8 @@ class EnvBase:
         return []
 
     # ------------------------------------------------------------------ episode tracer (trace.py)
-    # While a tracer is attached, step() issues its push launch after the step kernel (and after a recording launch):
-    # it reads the state planes and the step's reset / time_out outputs only.  With none attached nothing changes.
+    # While a tracer is attached, _after_step issues its push launch last: it reads the state planes and the step's
+    # reset / time_out outputs only.  With none attached nothing changes.
     _tracer = None
 
     def attach_tracer(self, tracer):

@@ -3,6 +3,10 @@
 torch provides device memory and the stream; every computation of the step runs
 in the HIP library legged_tracking_amd/_build/libgo1_mi355x.so.  If that library
 is missing or the GPU is absent this module raises -- there is no CPU fallback.
+
+It also holds what every binding of this package shares: load_library / check, the raw-stream partial, NativeHandle
+for the step handles, and the shim of the after-step add-ons (render.py, trace.py, plan.py, randomize.py):
+load_addon, dense, need_gpu and AddOn.
 """
 import ctypes as C
 import functools
@@ -55,6 +59,70 @@ def raw_stream_of(device):
 def raw_stream(device="cuda"):
     """The caller's current raw stream on `device`, for a call off the per-step path."""
     return raw_stream_of(device)()
+
+
+# ---------------------------------------------------------------------------- after-step add-ons
+_addons = {}
+
+
+def load_addon(path, prefix, version, argtypes, sizes=None):
+    """The add-on library at `path`, loaded once per path: load_library with <prefix>_abi_version and
+    <prefix>_last_error, then <prefix>_abi_sizes against `sizes`, the list the binding's ctypes mirrors give."""
+    l = _addons.get(path)
+    if l is None:
+        l = load_library(path, prefix + "_abi_version", version, prefix + "_last_error", argtypes)
+        if sizes is not None:
+            out = (C.c_int64 * len(sizes))()
+            getattr(l, prefix + "_abi_sizes")(out)
+            if list(out) != list(sizes):
+                raise NativeError(f"{path}: {prefix}_abi_sizes gives {list(out)}, the binding has {list(sizes)}")
+        _addons[path] = l
+    return l
+
+
+def dense(name, t, shape, dtypes, device=None, what=None):
+    """The data pointer of `t`, a contiguous tensor of `shape` and one of `dtypes`, on `device` where one is given;
+    NativeError otherwise.  An int `shape` is an element count: the flat form, which an (n,) and an (n, 1) plane
+    both meet.  `what` words the failure ("<name> must be <what>") for a caller that has a wording of its own."""
+    flat = isinstance(shape, int)
+    if t is None or (t.numel() != shape if flat else tuple(t.shape) != tuple(shape)) or t.dtype not in dtypes or \
+            not t.is_contiguous() or (device is not None and t.device != device):
+        if what is None:
+            what = "a contiguous %s %s tensor" % (f"({shape},) or ({shape}, 1)" if flat else tuple(shape),
+                                                 " / ".join(map(str, dtypes)))
+            if device is not None:
+                what += f" on {device}"
+        raise NativeError(f"{name} must be {what}")
+    return t.data_ptr()
+
+
+def need_gpu(device, what):
+    if device.type != "cuda":
+        raise NativeError(f"no GPU visible: the MI355X {what} has no CPU fallback")
+
+
+class AddOn:
+    """Base of the add-ons' launch owners (render.Renderer, trace.TraceBuffers, plan.PlanBuffers,
+    randomize.DrBuffers): the device, the caller's current raw stream on it and the return-code check.  One on a CPU
+    device can be built (the injected test backends do that) and loads nothing; only its launch raises."""
+    WHAT = "add-on"
+
+    def _open(self, device, lib):
+        """`lib` is the module's loader, called for a GPU device only."""
+        self.device = torch.device(device)
+        self._lib = None
+        if self.device.type == "cuda":
+            self._lib = lib()
+            self._stream = raw_stream_of(self.device)
+
+    def _need_gpu(self):
+        need_gpu(self.device, self.WHAT)
+
+    def _launch(self, fn, *args):
+        """Library function `fn`(*args, stream) on the caller's current stream."""
+        rc = getattr(self._lib, fn)(*args, self._stream())
+        if rc:
+            check(self._lib, rc)
 
 
 _ARGTYPES = {

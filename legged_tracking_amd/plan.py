@@ -7,14 +7,16 @@ of every scanned ceiling and floor point.  LocalPlanner enqueues one launch afte
 that does this for all envs and overwrites the commands columns of the step's observations; nothing synchronises
 until no_valid() is asked for.
 
-torch provides the device memory and the stream; the search runs in the HIP kernel (no CPU fallback)."""
+torch provides the device memory and the stream; the search runs in the HIP kernel (no CPU fallback).  The loader, the
+plane checks, the stream and the return-code check are native.py's add-on shim; EnvBase issues the launch
+(env_base.py, _after_step)."""
 import ctypes as C
 import os
 
 import numpy as np
 import torch
 
-from .native import NativeError, check, load_library
+from .native import AddOn, NativeError, dense, load_addon  # noqa: F401  (NativeError: importable from here)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "_build", "libgo1_plan.so")
@@ -53,7 +55,6 @@ _ARGTYPES = {
     "go1_plan_step": [C.POINTER(Go1PlanConfig), C.POINTER(Go1PlanTables), C.POINTER(Go1PlanState),
                       C.POINTER(Go1PlanArgs), C.c_void_p],
 }
-_lib = None
 
 
 def abi_sizes():
@@ -63,15 +64,7 @@ def abi_sizes():
 
 def lib():
     """The plan library, loaded once; its struct sizes are checked against the mirrors above."""
-    global _lib
-    if _lib is None:
-        l = load_library(LIB_PATH, "go1_plan_abi_version", GO1_PLAN_ABI_VERSION, "go1_plan_last_error", _ARGTYPES)
-        out = (C.c_int64 * 6)()
-        l.go1_plan_abi_sizes(out)
-        if list(out) != abi_sizes():
-            raise NativeError(f"{LIB_PATH}: struct sizes / caps {list(out)}, the binding has {abi_sizes()}")
-        _lib = l
-    return _lib
+    return load_addon(LIB_PATH, "go1_plan", GO1_PLAN_ABI_VERSION, _ARGTYPES, abi_sizes())
 
 
 def check_candidates(candidates):
@@ -122,22 +115,17 @@ def prepare_tables(candidates, grid_x, grid_y):
                 scan_y=gy)
 
 
-def _dense(name, t, shape, dtypes, device):
-    if t is None or tuple(t.shape) != tuple(shape) or t.dtype not in dtypes or not t.is_contiguous() or \
-            t.device != device:
-        raise NativeError(f"{name} must be a contiguous {tuple(shape)} {' / '.join(str(d) for d in dtypes)} tensor on "
-                          "the planner's device")
-
-
-class PlanBuffers:
+class PlanBuffers(AddOn):
     """The planner's tables and state on `device` and the launch, over caller-supplied planes (no env needed)."""
+    WHAT = "local planner"
 
     def __init__(self, n, device, candidates, grid_x, grid_y, traj_length, plan_interval, switch_dist, switch_yaw,
                  clip_obs, robot_size=ROBOT_SIZE):
         if int(plan_interval) <= 0:
             raise NameError("name 'ep_start' is not defined (Cfg.commands.plan_interval <= 0 with "
                             "sampling_based_planning, legged_robot_trajectory_tracking.py:867)")
-        self.device = dev = torch.device(device)
+        self._open(device, lib)
+        dev = self.device
         self.n = n = int(n)
         tb = prepare_tables(candidates, grid_x, grid_y)
         self.tables = {k: torch.from_numpy(tb[k]).to(dev) for k in ("cand", "foot", "cand_foot", "key_rot")}
@@ -150,7 +138,7 @@ class PlanBuffers:
         c.robot_size[:] = [float(x) for x in robot_size]
         c.scan_x[:self.nx] = [float(x) for x in tb["scan_x"]]
         c.scan_y[:self.ny] = [float(x) for x in tb["scan_y"]]
-        t = self._tables = Go1PlanTables(**{k: v.data_ptr() for k, v in self.tables.items()})
+        self._tables = Go1PlanTables(**{k: v.data_ptr() for k, v in self.tables.items()})
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
         self.local_target_poses = z((n, 6), torch.float32)
         self.plan_buf = z((n,), torch.bool)
@@ -168,48 +156,33 @@ class PlanBuffers:
             local_rel_lin=self.local_relative_linear.data_ptr(), local_rel_rot=self.local_relative_rotation.data_ptr(),
             replan=self.replan.data_ptr(), chosen=self.chosen.data_ptr(), no_valid_count=self.no_valid_count.data_ptr())
         self._args = Go1PlanArgs()
-        self._keep = None
-        if dev.type == "cuda":
-            self._fn = lib().go1_plan_step
-            self._stream_of = torch._C._cuda_getCurrentRawStream
-            self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
-        del t
 
     def launch(self, root, trajectory, curr_pose_index, episode_length, reset, heights, obs, obs_history=None,
                commands=None):
         """go1_plan_step on the current stream.  The planes are the step's post-step state and outputs; `commands`
         is an (n, >= 2) f32 view whose columns 0, 1 receive the commands (the aux block's, aux[:, 6:8])."""
-        if self.device.type != "cuda":
-            raise NativeError("no GPU visible: the MI355X local planner has no CPU fallback")
+        self._need_gpu()
         n, dev, a = self.n, self.device, self._args
         L = self._cfg.traj_length
         f32, i32, b8 = (torch.float32,), (torch.int32,), (torch.bool, torch.uint8)
-        _dense("root", root, (n, 13), f32, dev)
-        _dense("trajectory", trajectory, (n, 6 * L), f32, dev)
-        for name, t in (("curr_pose_index", curr_pose_index), ("episode_length", episode_length)):
-            if t is None or t.numel() != n or t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
-                raise NativeError(f"{name} must be a contiguous (n_envs,) or (n_envs, 1) int32 tensor")
-        _dense("reset", reset, (n,), b8, dev)
-        _dense("heights", heights, (n, 2, self.nx, self.ny), f32, dev)
+        a.root = dense("root", root, (n, 13), f32, dev)
+        a.trajectory = dense("trajectory", trajectory, (n, 6 * L), f32, dev)
+        a.curr_pose_index = dense("curr_pose_index", curr_pose_index, n, i32, dev)
+        a.episode_length = dense("episode_length", episode_length, n, i32, dev)
+        a.reset = dense("reset", reset, (n,), b8, dev)
+        a.heights = dense("heights", heights, (n, 2, self.nx, self.ny), f32, dev)
         if obs is None or obs.dim() != 2 or obs.shape[0] != n or obs.shape[1] < 5 or obs.dtype != torch.float32 or \
                 not obs.is_contiguous() or obs.device != dev:
             raise NativeError("obs must be a contiguous (n_envs, >= 5) float32 tensor")
-        if obs_history is not None:
-            _dense("obs_history", obs_history, obs.shape, f32, dev)
         if commands is not None and (commands.dim() != 2 or commands.shape[0] != n or commands.shape[1] < 2 or
                                      commands.dtype != torch.float32 or commands.stride(1) != 1 or
                                      commands.stride(0) < 2 or commands.device != dev):
             raise NativeError("commands must be an (n_envs, >= 2) float32 view with unit column stride")
-        a.root, a.trajectory, a.curr_pose_index = root.data_ptr(), trajectory.data_ptr(), curr_pose_index.data_ptr()
-        a.episode_length, a.reset, a.heights = episode_length.data_ptr(), reset.data_ptr(), heights.data_ptr()
         a.obs, a.obs_stride = obs.data_ptr(), int(obs.shape[1])
-        a.obs_history = obs_history.data_ptr() if obs_history is not None else None
+        a.obs_history = dense("obs_history", obs_history, obs.shape, f32, dev) if obs_history is not None else None
         a.commands = commands.data_ptr() if commands is not None else None
         a.commands_stride = int(commands.stride(0)) if commands is not None else 0
-        rc = self._fn(C.byref(self._cfg), C.byref(self._tables), C.byref(self._state), C.byref(a),
-                      self._stream_of(self._dev_index))
-        if rc:
-            check(lib(), rc)
+        self._launch("go1_plan_step", C.byref(self._cfg), C.byref(self._tables), C.byref(self._state), C.byref(a))
 
     def mark_reset(self, env_ids):
         """A host-initiated reset of `env_ids` (reset_idx :252-254), and idx_prev = ep_prev = 0: the reset trajectory

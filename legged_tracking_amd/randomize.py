@@ -8,14 +8,16 @@ rand_interval steps, and when it resets, its friction, restitution and (shadow) 
 enqueues one launch after each env step (LeggedRobot.step, VelocityTrackingEasyEnv.step) that does this for all envs
 on the step's own state planes and rewrites the privileged observation of the redrawn envs; nothing synchronises.
 
-torch provides the device memory and the stream; the draws run in the HIP kernel (no CPU fallback)."""
+torch provides the device memory and the stream; the draws run in the HIP kernel (no CPU fallback).  The loader, the
+plane check, the stream and the return-code check are native.py's add-on shim; EnvBase issues the two launches
+(env_base.py, _after_step and _after_reset_idx)."""
 import ctypes as C
 import os
 
 import numpy as np
 import torch
 
-from .native import NativeError, check, load_library
+from .native import AddOn, NativeError, dense, load_addon  # noqa: F401  (NativeError: importable from here)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "_build", "libgo1_dr.so")
@@ -25,6 +27,7 @@ U_PAYLOAD, U_FRICTION, U_RESTITUTION, U_PUSH_X, U_PUSH_Y = 0, 1, 2, 4, 5
 DR_TAG = 0x44520000                             # Philox counter word 1 = DR_TAG + block (GO1_DR_TAG)
 
 I32, F32, U64, P = C.c_int32, C.c_float, C.c_uint64, C.c_void_p
+F32_T = (torch.float32,)
 
 
 class Go1DrConfig(C.Structure):
@@ -52,7 +55,6 @@ _ARGTYPES = {
     "go1_dr_reset": [C.POINTER(Go1DrConfig), C.POINTER(Go1DrState), C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p,
                      C.c_void_p],
 }
-_lib = None
 
 
 def abi_sizes():
@@ -61,15 +63,7 @@ def abi_sizes():
 
 def lib():
     """The randomiser library, loaded once; its struct sizes are checked against the mirrors above."""
-    global _lib
-    if _lib is None:
-        l = load_library(LIB_PATH, "go1_dr_abi_version", GO1_DR_ABI_VERSION, "go1_dr_last_error", _ARGTYPES)
-        out = (C.c_int64 * 4)()
-        l.go1_dr_abi_sizes(out)
-        if list(out) != abi_sizes():
-            raise NativeError(f"{LIB_PATH}: struct sizes / caps {list(out)}, the binding has {abi_sizes()}")
-        _lib = l
-    return _lib
+    return load_addon(LIB_PATH, "go1_dr", GO1_DR_ABI_VERSION, _ARGTYPES, abi_sizes())
 
 
 def _flag(dr, name):
@@ -121,11 +115,12 @@ def _range(flag, rng):
     return int(bool(flag)), float(np.float32(hi - lo)), float(np.float32(lo))
 
 
-class DrBuffers:
+class DrBuffers(AddOn):
     """The randomiser's configuration, its payload shadow and the two launches on `device`, over caller-supplied planes
     (no env needed).  `ranges`: {"payload" | "friction" | "restitution": (lo, hi)} and "push": max_push_vel_xy;
     `flags`: {"rigids_after_start", "push_robots", "payload", "friction", "restitution": bool}; `priv`:
     (friction shift, friction scale, restitution shift, restitution scale, clip_obs)."""
+    WHAT = "domain randomiser"
 
     def __init__(self, n, device, ranges, flags, rand_interval, push_interval, priv, env_id_offset=0, seed=0,
                  payloads=None):
@@ -136,7 +131,8 @@ class DrBuffers:
                 raise ValueError(f"the {k} range {tuple(ranges[k])!r} has hi < lo")
         if ranges["push"] < 0:
             raise ValueError(f"max_push_vel_xy = {ranges['push']!r}: the push range has hi < lo")
-        self.device = dev = torch.device(device)
+        self._open(device, lib)
+        dev = self.device
         self.n = n = int(n)
         c = self._cfg = Go1DrConfig()
         c.n_envs, c.env_id_offset = n, int(env_id_offset)
@@ -158,26 +154,17 @@ class DrBuffers:
         self._state = Go1DrState()
         self._args = Go1DrArgs()
         self._keep = None
-        if dev.type == "cuda":
-            self._step_fn, self._reset_fn = lib().go1_dr_step, lib().go1_dr_reset
-            self._stream_of = torch._C._cuda_getCurrentRawStream
-            self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
-
-    def _plane(self, name, t, width, dtypes=(torch.float32,)):
-        if t is None or t.numel() != self.n * width or t.dtype not in dtypes or not t.is_contiguous() or \
-                t.device != self.device:
-            raise NativeError(f"{name} must be a contiguous ({self.n}, {width}) {' / '.join(map(str, dtypes))} tensor "
-                              "on the randomiser's device")
-        return t.data_ptr()
 
     def _bind(self, root, friction, restitution, payloads):
-        if self.device.type != "cuda":
-            raise NativeError("no GPU visible: the MI355X domain randomiser has no CPU fallback")
-        s = self._state
-        s.root = self._plane("root", root, 13)
-        s.friction = self._plane("friction", friction, 1)
-        s.restitution = self._plane("restitution", restitution, 1)
-        s.payloads = self._plane("payloads", self.payloads, 1) if payloads else None
+        self._need_gpu()
+        n, dev, s = self.n, self.device, self._state
+        s.root = dense("root", root, (n, 13), F32_T, dev)
+        s.friction = dense("friction", friction, n, F32_T, dev)
+        s.restitution = dense("restitution", restitution, n, F32_T, dev)
+        s.payloads = dense("payloads", self.payloads, n, F32_T, dev) if payloads else None
+
+    def _uniforms(self, name, u):
+        return dense(name, u, (self.n, DR_U), F32_T, self.device) if u is not None else None
 
     def launch(self, root, friction, restitution, episode_length, reset, rng_step, priv=None, uniforms=None,
                dbg_uniforms=None, payloads=True):
@@ -186,8 +173,8 @@ class DrBuffers:
         payloads=False leaves the payload shadow out of the launch."""
         self._bind(root, friction, restitution, payloads)
         a = self._args
-        a.reset = self._plane("reset", reset, 1, (torch.bool, torch.uint8))
-        a.episode_length = self._plane("episode_length", episode_length, 1, (torch.int32,))
+        a.reset = dense("reset", reset, self.n, (torch.bool, torch.uint8), self.device)
+        a.episode_length = dense("episode_length", episode_length, self.n, (torch.int32,), self.device)
         if priv is not None:
             if priv.dim() != 2 or priv.shape[0] != self.n or priv.shape[1] < 2 or priv.dtype != torch.float32 or \
                     not priv.is_contiguous() or priv.device != self.device:
@@ -196,22 +183,16 @@ class DrBuffers:
         else:
             a.priv, a.priv_stride = None, 0
         a.rng_step = int(rng_step)
-        a.uniforms = self._plane("uniforms", uniforms, DR_U) if uniforms is not None else None
-        a.dbg_uniforms = self._plane("dbg_uniforms", dbg_uniforms, DR_U) if dbg_uniforms is not None else None
-        rc = self._step_fn(C.byref(self._cfg), C.byref(self._state), C.byref(a), self._stream_of(self._dev_index))
-        if rc:
-            check(lib(), rc)
+        a.uniforms, a.dbg_uniforms = self._uniforms("uniforms", uniforms), self._uniforms("dbg_uniforms", dbg_uniforms)
+        self._launch("go1_dr_step", C.byref(self._cfg), C.byref(self._state), C.byref(a))
 
     def reset(self, root, friction, restitution, env_ids, rng_step, uniforms=None, payloads=True):
         """go1_dr_reset on the current stream: the rigid-props redraw of a host reset_idx(env_ids)."""
         self._bind(root, friction, restitution, payloads)
         ids = torch.as_tensor(env_ids, device=self.device).to(torch.int32).flatten().contiguous()
         self._keep = ids  # alive until the next call: the stream has passed it by then
-        up = self._plane("uniforms", uniforms, DR_U) if uniforms is not None else None
-        rc = self._reset_fn(C.byref(self._cfg), C.byref(self._state), ids.data_ptr(), int(ids.numel()), int(rng_step),
-                            up, self._stream_of(self._dev_index))
-        if rc:
-            check(lib(), rc)
+        self._launch("go1_dr_reset", C.byref(self._cfg), C.byref(self._state), ids.data_ptr(), int(ids.numel()),
+                     int(rng_step), self._uniforms("uniforms", uniforms))
 
 
 class Randomizer(DrBuffers):

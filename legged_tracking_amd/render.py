@@ -8,7 +8,10 @@ provides the device memory and the stream; every pixel is computed by the HIP ke
 Renderer keeps the reference's frame lists on the device: a frame ring of (max_episode_length + 1, 240, 360, 4)
 bytes and a state record the recording launch advances itself (go1_render_record), so a recorded step costs one
 launch and no device->host copy; get_complete_frames reads the record (a few bytes) when it is called and copies
-the finished episode to the host once."""
+the finished episode to the host once.
+
+The loader, the plane check, the stream and the return-code check are native.py's add-on shim; EnvBase issues the
+recording launch (env_base.py, _after_step)."""
 import ctypes as C
 import math
 import os
@@ -17,7 +20,7 @@ import numpy as np
 import torch
 
 from . import layout as L, model as M
-from .native import NativeError, check, load_library
+from .native import AddOn, NativeError, check, dense, load_addon, need_gpu, raw_stream
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "_build", "libgo1_render.so")
@@ -31,6 +34,7 @@ VIDEO_WIDTH, VIDEO_HEIGHT = 360, 240   # camera_props of the video camera (legge
 WAYPOINT_RADIUS = 0.04
 
 F, I32, P = C.c_float, C.c_int32, C.c_void_p
+F32 = (torch.float32,)
 
 
 class Go1RenderModel(C.Structure):
@@ -62,16 +66,12 @@ _ARGTYPES = {
     "go1_render": [C.POINTER(Go1RenderArgs), C.c_void_p],
     "go1_render_record": [C.POINTER(Go1RecordArgs), C.c_void_p],
 }
-_lib = None
 
 
 def lib():
-    """The render library, loaded once."""
-    global _lib
-    if _lib is None:
-        _lib = load_library(LIB_PATH, "go1_render_abi_version", GO1_RENDER_ABI_VERSION, "go1_render_last_error",
-                            _ARGTYPES)
-    return _lib
+    """The render library, loaded once; its struct sizes are checked against the mirrors above."""
+    return load_addon(LIB_PATH, "go1_render", GO1_RENDER_ABI_VERSION, _ARGTYPES,
+                      [C.sizeof(s) for s in (Go1RenderModel, Go1RenderView, Go1RenderArgs, Go1RecordArgs)])
 
 
 def model_struct():
@@ -121,19 +121,19 @@ class Scene:
         self.hs = float(horizontal_scale)
         self.trajectory, self.curr_pose_index = trajectory, curr_pose_index
         n = root.shape[0]
-        for name, t, shape, dt in (("root", root, (n, 13), torch.float32), ("dof_pos", dof_pos, (n, 12), torch.float32)):
-            _dense(name, t, shape, dt)
+        dense("root", root, (n, 13), F32)
+        dense("dof_pos", dof_pos, (n, 12), F32)
         if tiles is not None:
             if tiles.dim() != 4 or tiles.shape[1] != 2:
                 raise NativeError("tiles must be (n_tiles, 2, hf_nx, hf_ny)")
-            _dense("tiles", tiles, tuple(tiles.shape), torch.float32)
-            _dense("env_tile", env_tile, (n,), torch.int32)
-            _dense("env_terrain_origin", env_terrain_origin, (n, 3), torch.float32)
+            dense("tiles", tiles, tiles.shape, F32)
+            dense("env_tile", env_tile, (n,), (torch.int32,))
+            dense("env_terrain_origin", env_terrain_origin, (n, 3), F32)
         if trajectory is not None:
             if trajectory.dim() != 2 or trajectory.shape[1] % 6:
                 raise NativeError("trajectory must be (n_envs, 6 x length)")
-            _dense("trajectory", trajectory, (n, trajectory.shape[1]), torch.float32)
-            _dense("curr_pose_index", curr_pose_index, (n, 1), torch.int32)
+            dense("trajectory", trajectory, (n, trajectory.shape[1]), F32)
+            dense("curr_pose_index", curr_pose_index, (n, 1), (torch.int32,))
 
     def fill(self, a):
         a.model = model_struct()
@@ -149,33 +149,21 @@ class Scene:
             a.wp_length, a.wp_radius = int(self.trajectory.shape[1] // 6), WAYPOINT_RADIUS
 
 
-def _dense(name, t, shape, dtype):
-    if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
-        raise NativeError(f"{name} must be a contiguous {tuple(shape)} {dtype} tensor")
-
-
-def _stream(device):
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    return torch._C._cuda_getCurrentRawStream(idx)
-
-
 def render_views(scene, views, width, height, markers=None, depth=False, prim_id=False, out=None):
     """One go1_render launch on the current stream: `views` is a views_tensor; returns rgba (n_views, H, W, 4)
     uint8, then depth (f32) and prim_id (int32) when asked for.  `markers`: (n_views, m, 4) f32 or None."""
     dev = scene.root.device
-    if dev.type != "cuda":
-        raise NativeError("no GPU visible: the MI355X ray caster has no CPU fallback")
+    need_gpu(dev, Renderer.WHAT)
     nv = views.numel() // C.sizeof(Go1RenderView)
     a = Go1RenderArgs()
     scene.fill(a)
     a.views, a.n_views, a.width, a.height = views.data_ptr(), nv, int(width), int(height)
     rgba = out if out is not None else torch.empty((nv, height, width, 4), dtype=torch.uint8, device=dev)
-    _dense("rgba", rgba, (nv, height, width, 4), torch.uint8)
+    a.rgba = dense("rgba", rgba, (nv, height, width, 4), (torch.uint8,))
     res = [rgba]
-    a.rgba = rgba.data_ptr()
     if markers is not None:
-        _dense("markers", markers, (nv, markers.shape[1], 4), torch.float32)
-        a.markers, a.n_markers = markers.data_ptr(), int(markers.shape[1])
+        a.markers = dense("markers", markers, (nv, markers.shape[1], 4), F32)
+        a.n_markers = int(markers.shape[1])
     if depth:
         res.append(torch.empty((nv, height, width), dtype=torch.float32, device=dev))
         a.depth = res[-1].data_ptr()
@@ -183,16 +171,17 @@ def render_views(scene, views, width, height, markers=None, depth=False, prim_id
         res.append(torch.empty((nv, height, width), dtype=torch.int32, device=dev))
         a.prim_id = res[-1].data_ptr()
     with torch.cuda.device(dev):
-        check(lib(), lib().go1_render(C.byref(a), _stream(dev)))
+        check(lib(), lib().go1_render(C.byref(a), raw_stream(dev)))
     return res[0] if len(res) == 1 else tuple(res)
 
 
-class Renderer:
+class Renderer(AddOn):
     """The recorder of one env (EnvBase creates it at the first start_recording / render call)."""
+    WHAT = "ray caster"
 
     def __init__(self, env):
         self.env = env
-        self.device = env.device
+        self._open(env.device, lib)
         self.capacity = int(env.max_episode_length) + 1
         self.width, self.height = VIDEO_WIDTH, VIDEO_HEIGHT
         self.frames = self.state = None
@@ -282,18 +271,14 @@ class Renderer:
     def _record_launch(self, reset, step):
         a = self._args
         if a is None:
+            self._need_gpu()
             a = self._args = Go1RecordArgs()
             self.scene().fill(a.r)
             mode, flags = self.camera()
             v = self.views((0,), mode, flags)
             a.r.views, a.r.n_views, a.r.width, a.r.height = v.data_ptr(), 1, self.width, self.height
             a.r.rgba, a.state, a.capacity = self.frames.data_ptr(), self.state.data_ptr(), self.capacity
-            self._lib_record = lib().go1_render_record
-            self._stream_of = torch._C._cuda_getCurrentRawStream
-            self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        if reset.dtype != torch.bool or reset.shape != (a.r.n_envs,) or not reset.is_contiguous():
-            raise NativeError("reset must be the step's contiguous (n_envs,) bool output")
-        a.reset, a.step = reset.data_ptr(), step
-        rc = self._lib_record(C.byref(a), self._stream_of(self._dev_index))
-        if rc:
-            check(lib(), rc)
+        a.reset = dense("reset", reset, (a.r.n_envs,), (torch.bool,),
+                        what="the step's contiguous (n_envs,) bool output")
+        a.step = step
+        self._launch("go1_render_record", C.byref(a))

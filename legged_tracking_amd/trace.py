@@ -8,7 +8,9 @@ episode ends for a wanted cause, copies the episode out of the ring into a captu
 until counts() / episodes() are asked for.  A captured episode of T rows is drawn by handing its rows to the ray
 caster as T "envs": render_episode is one go1_render launch for the whole episode.
 
-torch provides the device memory and the stream; every copy is done by the HIP kernel (no CPU fallback)."""
+torch provides the device memory and the stream; every copy is done by the HIP kernel (no CPU fallback).  The loader,
+the plane check, the stream and the return-code check are native.py's add-on shim; EnvBase issues the push
+(env_base.py, _after_step)."""
 import ctypes as C
 import os
 from types import SimpleNamespace
@@ -16,7 +18,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from .native import NativeError, check, load_library
+from .native import AddOn, NativeError, dense, load_addon
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "_build", "libgo1_trace.so")
@@ -41,21 +43,11 @@ _ARGTYPES = {
     "go1_trace_abi_sizes": [C.POINTER(C.c_int64)],
     "go1_trace_push": [C.POINTER(Go1TraceArgs), C.c_void_p],
 }
-_lib = None
 
 
 def lib():
     """The trace library, loaded once; its struct size is checked against the mirror above."""
-    global _lib
-    if _lib is None:
-        l = load_library(LIB_PATH, "go1_trace_abi_version", GO1_TRACE_ABI_VERSION, "go1_trace_last_error", _ARGTYPES)
-        out = (C.c_int64 * 3)()
-        l.go1_trace_abi_sizes(out)
-        if list(out) != [C.sizeof(Go1TraceArgs), ROW, META]:
-            raise NativeError(f"{LIB_PATH}: go1_trace_args is {out[0]} bytes with rows of {out[1]} and meta of {out[2]} "
-                              f"words, the binding has {C.sizeof(Go1TraceArgs)}, {ROW}, {META}")
-        _lib = l
-    return _lib
+    return load_addon(LIB_PATH, "go1_trace", GO1_TRACE_ABI_VERSION, _ARGTYPES, [C.sizeof(Go1TraceArgs), ROW, META])
 
 
 def want_bits(want):
@@ -72,38 +64,34 @@ def want_bits(want):
     return bits
 
 
-def _dense(name, t, shape, dtypes):
-    if t is None or tuple(t.shape) != tuple(shape) or t.dtype not in dtypes or not t.is_contiguous():
-        raise NativeError(f"{name} must be a contiguous {tuple(shape)} {' / '.join(str(d) for d in dtypes)} tensor")
-
-
-class TraceBuffers:
+class TraceBuffers(AddOn):
     """The tracer's state and capture buffers over caller-supplied planes, and the push launch (no env needed).
     `trajectory` (n, 6 x length) and `wp_index` (n,) / (n, 1) int32 are each optional."""
+    WHAT = "episode tracer"
 
     def __init__(self, root, dof_pos, depth, capacity=64, want=TERMINATED | TIMEOUT, eligible=None, trajectory=None,
                  wp_index=None):
-        dev = root.device
+        self._open(root.device, lib)
+        dev = self.device
         n = int(root.shape[0])
-        self.device, self.n, self.depth, self.capacity = dev, n, int(depth), int(capacity)
+        self.n, self.depth, self.capacity = n, int(depth), int(capacity)
         if self.depth < 1 or self.capacity < 1:
             raise ValueError("depth and capacity must be >= 1")
         self.want = want_bits(want)
-        _dense("root", root, (n, 13), (torch.float32,))
-        _dense("dof_pos", dof_pos, (n, 12), (torch.float32,))
+        dense("root", root, (n, 13), (torch.float32,))
+        dense("dof_pos", dof_pos, (n, 12), (torch.float32,))
         self.root, self.dof_pos, self.trajectory, self.wp_index = root, dof_pos, trajectory, wp_index
         self.tw = 0
         if trajectory is not None:
             if trajectory.dim() != 2 or trajectory.shape[1] % 6 or trajectory.shape[1] == 0:
                 raise NativeError("trajectory must be (n_envs, 6 x length)")
-            _dense("trajectory", trajectory, (n, trajectory.shape[1]), (torch.float32,))
+            dense("trajectory", trajectory, (n, trajectory.shape[1]), (torch.float32,))
             self.tw = int(trajectory.shape[1])
-        if wp_index is not None and (wp_index.numel() != n or wp_index.dtype != torch.int32 or
-                                     not wp_index.is_contiguous()):
-            raise NativeError("wp_index must be a contiguous (n_envs,) or (n_envs, 1) int32 tensor")
+        if wp_index is not None:
+            dense("wp_index", wp_index, n, (torch.int32,))
         if eligible is not None:
             eligible = torch.as_tensor(eligible, device=dev)
-            _dense("eligible", eligible, (n,), (torch.bool, torch.uint8))
+            dense("eligible", eligible, (n,), (torch.bool, torch.uint8))
         self.eligible = eligible
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
         self.ring = z((self.depth, n, ROW), torch.int32)
@@ -128,24 +116,16 @@ class TraceBuffers:
             a.wp_trajectory, a.wp_length = trajectory.data_ptr(), self.tw // 6
             a.traj_start, a.cap_traj = self.traj_start.data_ptr(), self.cap_traj.data_ptr()
         a.n_envs, a.depth, a.capacity, a.want = n, self.depth, self.capacity, self.want
-        if dev.type == "cuda":
-            self._push_fn = lib().go1_trace_push
-            self._stream_of = torch._C._cuda_getCurrentRawStream
-            self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
 
     def push(self, reset, time_out):
         """The launch of one env step on the current stream: `reset` / `time_out` are the step's (n,) outputs."""
-        if self.device.type != "cuda":
-            raise NativeError("no GPU visible: the MI355X episode tracer has no CPU fallback")
+        self._need_gpu()
         a = self._args
-        for name, t in (("reset", reset), ("time_out", time_out)):
-            if t.dtype not in (torch.bool, torch.uint8) or t.shape != (self.n,) or not t.is_contiguous() or \
-                    t.device != self.device:
-                raise NativeError(f"{name} must be the step's contiguous (n_envs,) bool output")
-        a.reset, a.time_out, a.push = reset.data_ptr(), time_out.data_ptr(), self.pushes
-        rc = self._push_fn(C.byref(a), self._stream_of(self._dev_index))
-        if rc:
-            check(lib(), rc)
+        b8, what = (torch.bool, torch.uint8), "the step's contiguous (n_envs,) bool output"
+        a.reset = dense("reset", reset, (self.n,), b8, self.device, what)
+        a.time_out = dense("time_out", time_out, (self.n,), b8, self.device, what)
+        a.push = self.pushes
+        self._launch("go1_trace_push", C.byref(a))
         self.pushes += 1
 
     def mark_reset(self, env_ids):

@@ -412,11 +412,12 @@ class VelocityTrackingEasyEnv(EnvBase):
         """VelocityTrackingEasyEnv.step (__init__.py:22-44): obs, rew, reset, extras."""
         a = self._as_actions(actions)
         s = self._slot
+        out = self._out[s]
         args = self._args[s]
         if args is None:
             args = self._args[s] = self._sim.args()
-            args.obs, args.priv, args.rew = self._obs[s].data_ptr(), self._priv[s].data_ptr(), self._rew[s].data_ptr()
-            args.reset, args.time_out = self._reset[s].data_ptr(), self._time_out[s].data_ptr()
+            for k, v in out.items():
+                setattr(args, k, v.data_ptr())
             args.episode_log, args.episode_log_count = self._log.data_ptr(), self._log_count.data_ptr()
             args.episode_log_cap = self._log_cap
         # post_physics bookkeeping order (:120-121, :719-723): the step's gravity projection uses the vector
@@ -450,18 +451,13 @@ class VelocityTrackingEasyEnv(EnvBase):
         events = self.kernel_events.popleft() if self.kernel_events else None
         args.ev_begin, args.ev_end = events if events is not None else (None, None)
         self._sim.step(args)
-        if self._randomizer is not None:  # pushes and rigid props: behind the step's curriculum launch
-            self._randomizer.step(self._reset[s], self._priv[s], self._rng_step)
-        if self._rec is not None:  # a recording is armed: its launch follows the step's launches on the same stream
-            self._record_step(self._reset[s])
-        if self._tracer is not None:
-            self._tracer.push(self._reset[s], self._time_out[s])
+        self._after_step(out, hist)  # behind the step's curriculum launch
         self._last_hist = hist
         self._rng_step += 1
         self._slot = (s + 1) % OUT_RING
         self._last_actions_t = a
-        dict.__setitem__(self.extras, "privileged_obs", self._priv[s])
-        return self._obs[s], self._rew[s], self._reset[s], self.extras
+        dict.__setitem__(self.extras, "privileged_obs", out["priv"])
+        return out["obs"], out["rew"], out["reset"], self.extras
 
     def _make_extras(self):
         """The env's extras dict, built once: the VelocityTrackingEasyEnv.step numpy extras (:25-41) and
@@ -518,11 +514,8 @@ class VelocityTrackingEasyEnv(EnvBase):
         self._log_tag += 1
         self._sim.reset_idx(env_ids, rng_seed=self.seed, rng_step=(1 << 62) + self._rng_step, log=self._log,
                             log_count=self._log_count, log_tag=self._log_tag)
-        if self._randomizer is not None:
-            self._randomizer.reset_idx(env_ids, (1 << 62) + self._rng_step)
+        self._after_reset_idx(env_ids, (1 << 62) + self._rng_step)
         self._rng_step += 1
-        if self._tracer is not None:
-            self._tracer.mark_reset(env_ids)
         self._sim.extras_time_outs.copy_(self.time_out_buf)  # extras["time_outs"] rebinding (:251-252)
 
     def reset(self):

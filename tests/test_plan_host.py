@@ -239,8 +239,10 @@ def test_plan_library_is_built_as_the_step_kernels_and_shares_nothing_with_rende
     assert srcs == ["go1_plan.hip"] and flags == B.STEP_FLAGS
     files = {os.path.basename(x) for x in B.lib_files("libgo1_plan.so")}
     assert {"go1_plan.hip", "go1_plan.h", "go1_torch_math.h", "pmath.h"} <= files
-    for other in ("libgo1_render.so", "libgo1_trace.so"):
-        assert not files & {os.path.basename(x) for x in B.lib_files(other)}
+    for other in ("libgo1_render.so", "libgo1_trace.so"):  # nothing but the add-ons' host-side header
+        assert files & {os.path.basename(x) for x in B.lib_files(other)} == {"go1_host.h"}
+    for other in ("libgo1_mi355x.so", "libgo1_velocity.so", "libgo1_rollout.so", "libgo1_ppo.so"):
+        assert "go1_host.h" not in {os.path.basename(x) for x in B.lib_files(other)}
     # its own source and header belong to no other library
     for name in B.LIBS:
         if name != "libgo1_plan.so":

@@ -73,12 +73,16 @@ def test_argument_errors_are_reported_not_thrown():
 
 def test_render_library_keeps_the_step_libraries_build_as_it_was():
     """The ray caster is a library of its own with the plain flags; it shares no source or dependency with the
-    step libraries."""
+    step libraries, and with the other add-on libraries only their host-side header (go1_host.h: the error message
+    and the launch check, no device code)."""
     srcs, flags = B.LIBS["libgo1_render.so"]
     assert srcs == ["go1_render.hip"] and flags == []
-    other = set()
+    addons = ("libgo1_render.so", "libgo1_trace.so", "libgo1_plan.so", "libgo1_dr.so")
+    mine = {os.path.basename(x) for x in B.lib_files("libgo1_render.so")}
     for name in B.LIBS:
         if name != "libgo1_render.so":
-            other |= {os.path.basename(x) for x in B.lib_files(name)}
-    assert not ({os.path.basename(x) for x in B.lib_files("libgo1_render.so")} & other)
+            shared = mine & {os.path.basename(x) for x in B.lib_files(name)}
+            assert shared == ({"go1_host.h"} if name in addons else set()), (name, shared)
+    host = open(os.path.join(B.HERE, "csrc", "go1_host.h")).read()
+    assert "__global__" not in host and "__device__" not in host and '#include "' not in host
     assert "go1_model_consts.h" not in open(os.path.join(B.HERE, "csrc", "go1_render.hip")).read()

@@ -66,8 +66,10 @@ def test_argument_errors_are_reported_not_thrown():
 def test_trace_library_is_a_library_of_its_own():
     srcs, flags = B.LIBS["libgo1_trace.so"]
     assert srcs == ["go1_trace.hip"] and flags == []
-    other = set()
+    # it shares one file, and only with the other add-on libraries: their host-side header
+    addons = ("libgo1_render.so", "libgo1_trace.so", "libgo1_plan.so", "libgo1_dr.so")
+    mine = {os.path.basename(x) for x in B.lib_files("libgo1_trace.so")}
     for name in B.LIBS:
         if name != "libgo1_trace.so":
-            other |= {os.path.basename(x) for x in B.lib_files(name)}
-    assert not ({os.path.basename(x) for x in B.lib_files("libgo1_trace.so")} & other)
+            shared = mine & {os.path.basename(x) for x in B.lib_files(name)}
+            assert shared == ({"go1_host.h"} if name in addons else set()), (name, shared)
