@@ -34,6 +34,10 @@ LIBS = {
     # the after-start domain randomiser (randomize.py): one launch after the step kernel, built with the planner's
     # flags: it uses the step kernels' Philox and clampf, and its u * range + lo must stay a multiply and an add
     "libgo1_dr.so": (["go1_dr.hip"], STEP_FLAGS),
+    # the privileged-observation assembler (privileged.py): one launch after the step kernel, built with the
+    # randomiser's flags: its (x - shift) * scale must stay a subtraction and a multiply.  Its only files are its own
+    # source and header (no go1_host.h: see the note in go1_priv.hip)
+    "libgo1_priv.so": (["go1_priv.hip"], STEP_FLAGS),
     # test-only: one thin kernel per device function of go1_device.h (tests/devcheck.py), built as the step kernels are
     "libgo1_devcheck.so": (["go1_devcheck.hip"], STEP_FLAGS),
 }

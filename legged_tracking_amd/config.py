@@ -1004,6 +1004,9 @@ def build_abi_config(cfg, n_envs=None, physics=None, actuator=None, hf_shape=(80
     if randomizer and any(bool(_get(cfg, p, False)) for p in _RANDOMIZER_PATHS):
         from . import randomize
         randomize.check_randomizer(cfg)
+    # the priv_observe_* flags: the reference's own width assert (:589-590) and its ground-friction failure (:493)
+    from . import privileged
+    privileged.check(cfg)
     physics = dict(PHYSICS, **(physics or {}))
     d = derived(cfg)
     c = abi.Go1Config()

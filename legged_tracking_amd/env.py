@@ -323,6 +323,7 @@ class LeggedRobot(EnvBase):
             from . import plan
             self._planner = plan.LocalPlanner(self)
         self._init_randomizer()
+        self._init_privileged()
         # which per-step outputs the kernel stores beyond obs / rewards / resets (set_output_demand)
         self._demand = (True, True)
         # envs the native integrator's divergence guard reset, cumulative (extras["diverged"])
@@ -400,6 +401,11 @@ class LeggedRobot(EnvBase):
         (ppo_cse/__init__.py:164-214), and restores them; reading one while it is off raises instead of returning
         a stale step."""
         self._demand = (bool(contact_forces), bool(aux))
+
+    def _stores_aux(self):
+        """Whether the step stores the aux block: on demand, and always while the privileged observation reads
+        base_lin_vel from it (priv_observe_body_velocity); reading it through the env still follows the demand."""
+        return self._demand[1] or (self._privileged is not None and self._privileged.needs_aux)
 
     def _aux_view(self, a, b):
         if not self._demand[1]:
@@ -492,8 +498,8 @@ class LeggedRobot(EnvBase):
             if self._planner is not None:
                 cf["debug"] = {"heights": self._planner.heights}
             self._sim.step(a, self._gravity_vec, self._sim_gravity, self._scale_vector(), rng_seed=self.seed,
-                           rng_step=self._rng_step, out=out, episode_log=self._elog.next_slot(),
-                           aux=self._aux if self._demand[1] else None, obs_history=hist, events=events,
+                           rng_step=self._rng_step, out=self._kout[s], episode_log=self._elog.next_slot(),
+                           aux=self._aux if self._stores_aux() else None, obs_history=hist, events=events,
                            diverged_count=self._diverged, **cf)
         self._after_step(out, hist)
         self._last_hist = hist
@@ -502,20 +508,20 @@ class LeggedRobot(EnvBase):
         self._slot = (s + 1) % OUT_RING
         # post-physics host bookkeeping (:126, :826-830, :171-182)
         self._tick_gravity_schedule()
+        self._after_tick(out)
         self.update_curriculum()
         return out["obs"], out["priv"], out["rew"], out["reset"], self.extras
 
     def _prepare_slot(self, s, log):
         """Validated go1_step_args for output-ring slot s and this episode-log buffer."""
-        out = self._out[s]
         hist = self._obs_hist[s] if self._obs_hist is not None else None
         el = self._elog
-        args = self._sim.prepare(out, aux=self._aux if self._demand[1] else None, obs_history=hist,
+        args = self._sim.prepare(self._kout[s], aux=self._aux if self._stores_aux() else None, obs_history=hist,
                                  diverged_count=self._diverged, episode_log=log,
                                  log_count=el.count[el.half] if el.compact else None,
                                  contact_forces=self._demand[0],
                                  **({} if self._planner is None else {"heights": self._planner.heights}))
-        return args, out, hist
+        return args, self._out[s], hist
 
     def update_curriculum(self):
         """update_curriculum (:171-182): exploration scales decay after exploration_steps."""

@@ -4,7 +4,8 @@ EnvBase owns the rank / world-size resolution, dims and seed, the OUT_RING outpu
 views and per-slot dicts, the state views, the per-env Philox draws keyed by global env id (creation-time domain
 randomisation), the global gravity schedule (_randomize_gravity, _tick_gravity_schedule), the action and
 env-id normalisation, the twelve lazy numpy extras, the reference's recording / render surface (render.py) and the
-one path of the add-on launches behind the step kernel and behind a host reset_idx (_after_step, _after_reset_idx).
+one path of the add-on launches behind the step kernel and behind a host reset_idx (_after_step, _after_tick,
+_after_reset_idx).
 
 Each env keeps what differs: when its step ticks the gravity schedule (after the launch / before it, with
 the pre- and post-tick vectors), the initial gravity draw (trajectory only), its aux column layout,
@@ -104,6 +105,7 @@ class EnvBase:
         # the views of one slot, as a step hands them to the kernel, to the add-ons and to its caller
         self._out = [dict(obs=self._obs[s], priv=self._priv[s], rew=self._rew[s], reset=self._reset[s],
                           time_out=self._time_out[s]) for s in range(OUT_RING)]
+        self._kout = self._out  # what the step kernel is handed; _init_privileged gives it a priv buffer of its own
         self._slot = 0
         self._last_hist = None
         # _randomize_rigid_body_props at creation: per-env draws keyed by GLOBAL env id (every rank draws the
@@ -236,6 +238,7 @@ class EnvBase:
     # ------------------------------------------------------------------ add-on launches
     _randomizer = None       # randomize.Randomizer, built by _init_randomizer when the Cfg sets one of its flags
     _planner = None          # plan.LocalPlanner, built by the trajectory env when its Cfg plans
+    _privileged = None       # privileged.Privileged, built by the trajectory env for a priv_observe_* set of its own
 
     def _after_step(self, out, hist):
         """The add-ons' launches of one step, behind the step kernel on its stream, each only if present: `out` is
@@ -243,13 +246,20 @@ class EnvBase:
         the behaviour: the randomiser rewrites priv before anything reads it, and the planner rewrites obs (and the
         commands of the trajectory env's aux block) before the recorder or the tracer run."""
         if self._randomizer is not None:
-            self._randomizer.step(out["reset"], out["priv"], self._rng_step)
+            # the step's own two columns; with the assembler behind it (_after_tick) nothing reads them
+            self._randomizer.step(out["reset"], out["priv"] if self._kout is self._out else None, self._rng_step)
         if self._planner is not None:
             self._planner.step(out, self._planner.heights, hist, self._aux if self._demand[1] else None)
         if self._rec is not None:
             self._record_step(out["reset"])
         if self._tracer is not None:
             self._tracer.push(out["reset"], out["time_out"])
+
+    def _after_tick(self, out):
+        """The launch that reads what the step's tick of the gravity schedule changes, behind _after_step and the
+        tick: the privileged observation of the step (compute_observations sees the schedule's draw, :826-830)."""
+        if self._privileged is not None:
+            self._privileged.step(out["priv"], self.gravities)
 
     def _after_reset_idx(self, env_ids, rng_step):
         """What the add-ons are told of a host reset_idx(env_ids), behind the env's own reset launch: the randomiser
@@ -274,6 +284,33 @@ class EnvBase:
     def randomizer(self):
         """The Randomizer behind this env, or None when the Cfg sets neither of its flags."""
         return self._randomizer
+
+    # ------------------------------------------------------------------ privileged observations (privileged.py)
+    # With a priv_observe_* set other than friction and restitution, the step kernel writes its two columns into an
+    # (n, 2) buffer nothing reads and the assembler's launch fills the step's slot of the (OUT_RING, n, W) ring; with
+    # exactly those two nothing is built and the kernel writes the ring itself, as before.
+
+    def _init_privileged(self):
+        from . import privileged
+        if privileged.wanted(self.cfg):
+            step_priv = torch.zeros((self.num_envs, 2), device=self.device)
+            self._kout = [dict(o, priv=step_priv) for o in self._out]
+            if self.num_privileged_obs > 0:  # no flag at all: an (n, 0) vector, nothing to assemble
+                self._privileged = privileged.Privileged(self)
+
+    @property
+    def privileged(self):
+        """The Privileged assembler behind this env (names, width), or None when the step kernel's own two columns
+        are the whole vector."""
+        return self._privileged
+
+    @property
+    def motor_strengths(self):
+        return self._sim.state["motor_strength"]
+
+    @property
+    def motor_offsets(self):
+        return self._sim.state["motor_offset"]
 
     @property
     def friction_coeffs(self):
